@@ -10,11 +10,13 @@ One ELBO-eval = one log-importance-weight log w[k, b], so a step does B*K evals 
   python bench.py [--gpus N --steps K --warmup W]          (N > 1: this process only starts the N ranks, see launch_ranks)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (the driver's form for N > 1)
 
-Timing: trials of EXACTLY `--steps` steps, each bracketed by torch.cuda.synchronize() + a barrier on both sides and
-reduced with MAX over the ranks; trials repeat until at least MIN_TIMED_SECONDS have been timed (so that `--steps 20` is
-not a 24 ms sample) and the MEDIAN trial is reported.
+Timing: EXACTLY `--steps` steps in one window, bracketed by torch.cuda.synchronize() + a barrier on both sides and reduced
+with MAX over the ranks; `ms_per_step` is that window over `--steps`.
 
-Rank 0 prints ONE JSON line (contract in the task description; kept under 8 KB) with
+A plain run sets up, warms up (`--warmup` steps), times the steps, writes the last step's outputs (`--dump-outputs DIR`)
+and prints the line with the headline figure.  Everything else it can measure or check runs only with `--full`.
+
+Rank 0 prints ONE JSON line (contract in the task description; kept under 8 KB) with, under `--full`,
   `roofline`      the hot-path kernel that moves the most bytes per step (the backward of the Bernoulli stream), timed live
                   in the launch mode of the timed region, plus flat scalars for the other kernels the contract names:
                   `k1_frac_1M`, `k1_frac_4M` (the fused Normal sample + log-prob kernel beyond the cache), `k3_fwd_frac`,
@@ -45,7 +47,7 @@ for p in (ROOT, os.path.join(ROOT, "zhusuan-pytorch_amd"), os.path.join(ROOT, "t
 
 BATCH_PER_GPU, PARTICLES, Z_DIM, X_DIM, HIDDEN = 256, 50, 40, 784, 500
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
-MIN_TIMED_SECONDS = 0.5
+DEFAULT_GEMM_PICKS = os.path.join(ROOT, "bench_gemm_picks.csv")
 
 
 def parse_args(argv=None):
@@ -53,12 +55,18 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure as well: the per-kernel timing passes and the "
+                         "roofline, the K1 and HBM-resident kernel figures, extra_configs, the CPU baselines, the same-process twin "
+                         "of --force-collective-path, the replica check of several ranks and the full record (--full-record)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--fused-logits", action="store_true",
                     help="the decoder hands logits to Bernoulli(logits=...): its final sigmoid is formed inside the log-prob "
                          "kernel instead of a separate pass over [K, B, 784] (extra_configs.c3_logits in the default run; the "
                          "default keeps the nn.Sigmoid pass and Bernoulli(probs=...) of the reference's example)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip extra_configs and the HBM-resident kernel figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip extra_configs and the HBM-resident kernel figures")
     ap.add_argument("--force-collective-path", action="store_true",
                     help="run the multi-rank code path (bucket pack + all-reduce + split graphs) even with one rank")
     ap.add_argument("--overlap", action="store_true",
@@ -69,9 +77,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-direct-rccl", action="store_true",
                     help="all-reduce through torch.distributed (two HIP event records per call) instead of this job's own RCCL "
                          "communicator driven on the compute stream (zhusuan.dataparallel.DirectAllReduce)")
-    ap.add_argument("--gemm-picks", default="",
-                    help="(set by the parent of the c3_dp_step_n1 child) a TunableOp results file to start from: the same GEMM kernels "
-                         "as the process that wrote it")
+    ap.add_argument("--gemm-picks", default=DEFAULT_GEMM_PICKS,
+                    help="a TunableOp results file to start from: its GEMM picks are used as they are, only shapes it lacks are tuned.  "
+                         "Default: bench_gemm_picks.csv next to this script (the fastest fp32 solutions for the workloads' shapes, timed "
+                         "on an MI355X), so that every run computes with the same GEMM kernels; \"\" times every shape afresh.  The "
+                         "parent of the c3_dp_step_n1 child passes its own picks")
     ap.add_argument("--timeline", default="",
                     help="write a chrome trace (torch.profiler: host runtime calls + device activity) of 5 steps in the timed "
                          "region's launch mode to this path (tools/timeline_gaps.py reads it)")
@@ -99,7 +109,7 @@ def parse_args(argv=None):
                          "the default run)")
     ap.add_argument("--reference-draws", action="store_true", help="(default since round 4; kept for old command lines)")
     ap.add_argument("--full-record", default=os.path.join(ROOT, "bench_full.json"),
-                    help="where the long-form record goes (per-kernel tables, trial times, setting descriptions)")
+                    help="where the long-form record of --full goes (per-kernel tables, trial times, setting descriptions)")
     ap.add_argument("--torch-linear", action="store_true",
                     help="build the callers' MLPs from torch.nn.Linear / Sequential (as the reference's examples do) instead of "
                          "zhusuan.Linear / zhusuan.Sequential -- the same layers (parameters, names, GEMMs) with the ReLU in the forward "
@@ -185,18 +195,32 @@ def baseline_metric():
 GEMM_PICKS = {"loaded_from": None}
 
 
-def gemm_picks_file():
+def gemm_picks_file(kind="tuned"):
     import tempfile                  # TunableOp writes its picks there: keep that file out of the repository
-    return os.path.join(tempfile.gettempdir(), "zs_bench_tunableop_%d.csv" % os.getpid())
+    return os.path.join(tempfile.gettempdir(), "zs_bench_tunableop_%s%d.csv" % ("" if kind == "tuned" else kind + "_", os.getpid()))
+
+
+def save_gemm_picks(path):
+    """Every TunableOp pick this process holds -- read from a file or tuned here -- as one results file another process can
+    start from (TunableOp's own file receives only the shapes tuned in this process)."""
+    import torch.cuda.tunable as tunable
+    with open(path, "w") as f:
+        for key, value in tunable.get_validators():
+            f.write("Validator,%s,%s\n" % (key, value))
+        for op, params, kernel, duration in tunable.get_results():
+            f.write("%s,%s,%s,%s\n" % (op, params, kernel, duration))
+    return path
 
 
 def gemm_tuning(on, tune=True, picks=None):
     """The callers' MLPs (outside the hot path, 72 % of the step) are fp32 GEMMs dispatched by PyTorch.  Its TunableOp
     times the available fp32 hipBLASLt / rocBLAS solutions for each GEMM shape once (during the eager warm-up steps,
     ~4 s in total for this workload) and uses the fastest from then on: same precision, same arithmetic, another tiling.
-    `--no-gemm-tuning` measures with PyTorch's default heuristic selection.  `picks`: a results file of ANOTHER process to start
-    from (the one-rank child of c3_dp_step_n1 takes its parent's: the two processes then run the same GEMM kernels, and what is
-    left of `vs_headline` is the step's form, not two tuning runs' different winners); shapes it lacks are tuned as usual."""
+    `--no-gemm-tuning` measures with PyTorch's default heuristic selection.  `picks`: a results file to start from -- by default
+    bench_gemm_picks.csv: near-ties between solutions come out differently from run to run, and the last-bit differences of two
+    sets of GEMM kernels grow over a few hundred Adam steps into a different trained state; with the committed picks every run
+    computes the same step.  The one-rank child of c3_dp_step_n1 takes its parent's picks: the two processes then run the same
+    GEMM kernels, and what is left of `vs_headline` is the step's form.  Shapes the file lacks are tuned as usual."""
     try:
         import torch.cuda.tunable as tunable
         tunable.enable(bool(on))
@@ -208,7 +232,8 @@ def gemm_tuning(on, tune=True, picks=None):
                 try:
                     ok = tunable.read_file(picks)
                     GEMM_PICKS["loaded_from"] = picks if ok else None
-                    sys.stderr.write("bench: GEMM picks of another process %s (%s)\n" % ("loaded" if ok else "NOT loaded", picks))
+                    sys.stderr.write("bench: GEMM picks %s %s (%s)\n" % ("committed with bench.py" if picks == DEFAULT_GEMM_PICKS else
+                                                                          "of another process", "loaded" if ok else "NOT loaded", picks))
                 except Exception as e:                              # noqa: BLE001
                     sys.stderr.write("bench: could not read the GEMM picks %s (%r); tuning afresh\n" % (picks, e))
         return bool(on)
@@ -408,9 +433,9 @@ def cpu_baseline(name="c3", budget_s=8.0, one_thread_budget_s=5.0, max_steps=40,
 
 
 # ------------------------------------------------------------------------------------------------ timing helpers
-def timed_trials(step, steps, world, dev, min_seconds=MIN_TIMED_SECONDS, max_trials=200, kick=None):
+def timed_trials(step, steps, world, dev, min_seconds=0.0, max_trials=200, kick=None):
     """Trials of exactly `steps` steps, each bracketed by synchronize + barrier and reduced with MAX over the ranks;
-    at least three and as many as it takes to cover `min_seconds`.
+    at least three (or `max_trials` if fewer) and as many as it takes to cover `min_seconds`.
     Returns (list of elapsed seconds per trial, last loss)."""
     def one():
         torch.cuda.synchronize()
@@ -552,9 +577,9 @@ def dp_step_on_one_rank(args, headline_value, timeout_s=240):
         port = sk.getsockname()[1]
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--force-collective-path", "--no-extras", "--no-cpu-baseline", "--full-record", os.devnull]
-    if not args.no_gemm_tuning and os.path.exists(gemm_picks_file()):
-        cmd += ["--gemm-picks", gemm_picks_file()]          # the child runs THIS process's GEMM kernels
+           "--force-collective-path", "--full", "--no-extras", "--no-cpu-baseline", "--full-record", os.devnull]
+    if not args.no_gemm_tuning:
+        cmd += ["--gemm-picks", save_gemm_picks(gemm_picks_file("all"))]          # the child runs THIS process's GEMM kernels
     for flag, on in (("--fused-logits", args.fused_logits), ("--torch-adam", args.torch_adam), ("--torch-linear", args.torch_linear),
                      ("--no-gemm-tuning", args.no_gemm_tuning), ("--skip-discarded-draws", args.skip_discarded_draws),
                      ("--allow-experiments", args.allow_experiments), ("--unfused-activations", args.unfused_activations)):
@@ -843,6 +868,22 @@ def fit_line(out, limit=LINE_LIMIT):
     return line
 
 
+def dump_outputs(directory, model, loss, grad_scale):
+    """--dump-outputs: what the last timed step computed, as its caller receives it -- `loss` (the objective, float64, 0-d),
+    `iw_bound` (the forward's per-datapoint importance-weighted bound), `param.<name>` (every parameter after the step's update) and
+    `grad.<name>` (the gradients of the step's backward, averaged over the ranks) -- one float32 / float64 .npy each, about 11 MB
+    at the headline shape.  The inputs (data, initial weights, Philox streams) are seeded and the GEMM kernels are the committed
+    picks (gemm_tuning): the same arguments give the same arrays, bit for bit."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"loss": np.asarray(loss, dtype=np.float64), "iw_bound": model.last_iw_bound.detach().float().cpu().numpy()}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            arrays["grad." + name] = (p.grad.detach().float() * grad_scale).cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
 
@@ -901,7 +942,7 @@ def main():
         _ops.IW1_MAX_STREAM_BYTES = args.iw1_max_stream_bytes
 
     k1_first = {}
-    if world == 1 and rank == 0 and not args.no_extras and not args.force_collective_path:
+    if args.full and world == 1 and rank == 0 and not args.no_extras and not args.force_collective_path:
         try:
             k1_first = k1_resident(_hip.lib(), dev)
         except Exception as e:                                      # noqa: BLE001
@@ -952,11 +993,9 @@ def main():
         shared = os.path.join(tempfile.gettempdir(), "zs_bench_tunableop_job_%s.csv" % os.environ.get("MASTER_PORT", "0"))
         kick("GEMM picks of rank 0")
         try:
-            import torch.cuda.tunable as tunable
             if rank == 0:
                 if os.path.exists(shared):
                     os.remove(shared)
-                tunable.set_filename(shared)
                 # (torch.autograd.grad, not backward(): the parameters' AccumulateGrad nodes remember the stream they first ran on, and a
                 #  first use on the default stream breaks the capture that follows -- a segfault in capture_end, seen once here)
                 #  and on a side stream, like the warm-up of the capture itself: nothing of the step touches the default stream before it
@@ -969,6 +1008,7 @@ def main():
                         torch.autograd.grad(model(obs), params_, grad_outputs=one, allow_unused=True)
                 torch.cuda.current_stream().wait_stream(pre)
                 torch.cuda.synchronize()
+                save_gemm_picks(shared)
         except Exception as e:                                      # noqa: BLE001
             sys.stderr.write("bench: rank %d: pre-tuning failed (%r); every rank tunes for itself\n" % (rank, e))
         dist.barrier()
@@ -1138,13 +1178,15 @@ def main():
         gemm_tuning(tuned, tune=False)       # the warm-up has seen every GEMM shape of the step: keep the picks, stop timing
         if rank == stall_rank:              # test hook: this rank stops here; its peers wait in the first trial's barrier
             time.sleep(10 ** 6)
-        trials, last = timed_trials(step, args.steps, world, dev, kick=kick)
+        trials, last = timed_trials(step, args.steps, world, dev, max_trials=1, kick=kick)      # exactly --steps timed steps
         # (read here: the same-process twin below trains the same model on -- tools/gpu_job.sh dp_soak compares the forms at equal step counts)
         final_loss = float(last) * (grad_scale if slot_is_sum else 1.0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, model, final_loss, grad_scale if slot_is_sum else 1.0)
         # one rank on the collective path: the SAME model, optimizer, GEMM picks and box as a single graph, alternating with
         # the multi-rank form -- what the path costs before a byte crosses xGMI, free of process-to-process differences
         same_process = None
-        if args.force_collective_path and world == 1 and mode.startswith("hipgraph"):
+        if args.full and args.force_collective_path and world == 1 and mode.startswith("hipgraph"):
             from zhusuan import _ops
 
             def compute_single():          # the headline step exactly: gradients allocated by autograd, no bucket involved
@@ -1166,56 +1208,58 @@ def main():
                             "collective_path_vs_single_graph": m_single / m_multi,
                             "extra_us_per_step": 1e6 * (m_multi - m_single) / args.steps, "trials_each": len(t_multi)}
             del twin
-        kick("per-kernel timing passes")
         elapsed = float(np.median(trials))
-        # per-kernel durations: the same steps launched eagerly with start/stop HIP events bound to each
-        # kernel dispatch on its stream (events cannot ride inside a graph replay)
-        n_prof = min(args.steps, 50)
-        # bytes of the callers' layer kernels (AB1 / CS1: one launch per dense layer, shapes differ): their arguments, from the calls
-        layer_bytes, real_call = {}, klib.call
-
-        def spy(name, *a):
-            if name == "zs_dense_act_bwd_f32":
-                layer_bytes[name] = layer_bytes.get(name, 0) + 12 * a[5] * a[6] + 4 * a[6]       # read g, y; write gpre, bias gradient
-            elif name == "zs_column_sum_f32":
-                layer_bytes[name] = layer_bytes.get(name, 0) + 4 * a[2] * a[3] + 4 * a[3]
-            return real_call(name, *a)
-
-        def eager_steps(n):
-            if mode != "eager" and not hooks:
-                side = torch.cuda.Stream()       # eager launches next to captured graphs: stay off the default stream
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(n):
-                        step_body()
-                torch.cuda.current_stream().wait_stream(side)
-            else:
-                for _ in range(n):
-                    step_body()
-            torch.cuda.synchronize()
-        klib.call = spy
-        try:
-            eager_steps(1)
-        finally:
-            klib.call = real_call
-        klib.prof_enable(True)
-        eager_steps(n_prof)
-        klib.prof_enable(False)
-        # the same kernels timed in the launch mode of the timed region (graph replays): device timestamps per dispatch
-        n_dev = min(args.steps, 30)
 
         def run_steps(n):
             for _ in range(n):
                 step()
-        # an external tracer (rocprofv3) owns the activity records: kineto then returns garbage durations
-        external_tracer = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or \
-            "rocprofiler-sdk-tool" in os.environ.get("LD_PRELOAD", "")
-        if rank == 0 and not external_tracer and os.environ.get("ZS_BENCH_NO_TRACER") != "1":
-            dev_times = device_kernel_times(run_steps, n_dev)
-        else:
-            run_steps(n_dev)
-            dev_times = {}
-        torch.cuda.synchronize()
+
+        if args.full:
+            kick("per-kernel timing passes")
+            # per-kernel durations: the same steps launched eagerly with start/stop HIP events bound to each
+            # kernel dispatch on its stream (events cannot ride inside a graph replay)
+            n_prof = min(args.steps, 50)
+            # bytes of the callers' layer kernels (AB1 / CS1: one launch per dense layer, shapes differ): their arguments, from the calls
+            layer_bytes, real_call = {}, klib.call
+
+            def spy(name, *a):
+                if name == "zs_dense_act_bwd_f32":
+                    layer_bytes[name] = layer_bytes.get(name, 0) + 12 * a[5] * a[6] + 4 * a[6]       # read g, y; write gpre, bias gradient
+                elif name == "zs_column_sum_f32":
+                    layer_bytes[name] = layer_bytes.get(name, 0) + 4 * a[2] * a[3] + 4 * a[3]
+                return real_call(name, *a)
+
+            def eager_steps(n):
+                if mode != "eager" and not hooks:
+                    side = torch.cuda.Stream()       # eager launches next to captured graphs: stay off the default stream
+                    side.wait_stream(torch.cuda.current_stream())
+                    with torch.cuda.stream(side):
+                        for _ in range(n):
+                            step_body()
+                    torch.cuda.current_stream().wait_stream(side)
+                else:
+                    for _ in range(n):
+                        step_body()
+                torch.cuda.synchronize()
+            klib.call = spy
+            try:
+                eager_steps(1)
+            finally:
+                klib.call = real_call
+            klib.prof_enable(True)
+            eager_steps(n_prof)
+            klib.prof_enable(False)
+            # the same kernels timed in the launch mode of the timed region (graph replays): device timestamps per dispatch
+            n_dev = min(args.steps, 30)
+            # an external tracer (rocprofv3) owns the activity records: kineto then returns garbage durations
+            external_tracer = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or \
+                "rocprofiler-sdk-tool" in os.environ.get("LD_PRELOAD", "")
+            if rank == 0 and not external_tracer and os.environ.get("ZS_BENCH_NO_TRACER") != "1":
+                dev_times = device_kernel_times(run_steps, n_dev)
+            else:
+                run_steps(n_dev)
+                dev_times = {}
+            torch.cuda.synchronize()
         if args.timeline and rank == 0:
             try:
                 from torch.profiler import profile, ProfilerActivity
@@ -1231,7 +1275,7 @@ def main():
         # every replica started from rank 0's weights and applied the same averaged gradients: their parameters must be
         # bit-identical after any number of steps.  A collective that summed the wrong buffers shows up here.
         replicas = None
-        if world > 1 and dist.is_initialized():
+        if args.full and world > 1 and dist.is_initialized():
             kick("replica check")
             with torch.no_grad():
                 flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).double()
@@ -1270,62 +1314,70 @@ def main():
             "zs_bernoulli_iw_objective_bwd_f32": ((8 * N * X + 4 * B * X + 4 * N) if N <= 32768 else 0) + (4 * N * D + 4 * N + 16 * B * D),
             "zs_adam_step_f32": 28 * sum(p.numel() for p in model.parameters()),  # read p, g, m, v; write p, m, v
         }
-        # the IW kernels serve two entry points; the tracer sees kernel names only
-        if "zs_iw_reduce_f32" in dev_times and klib.prof_query("zs_iw_objective_f32")["count"] and \
-                not klib.prof_query("zs_iw_reduce_f32")["count"]:
-            dev_times["zs_iw_objective_f32"] = dev_times.pop("zs_iw_reduce_f32")
-        # ... and so does the flat-plane sampling kernel (one draw / both draws of a latent)
-        if "zs_normal_sample_logprob_f32" in dev_times and klib.prof_query("zs_normal_sample_logprob_pair_f32")["count"] and \
-                not klib.prof_query("zs_normal_sample_logprob_f32")["count"]:
-            dev_times["zs_normal_sample_logprob_pair_f32"] = dev_times.pop("zs_normal_sample_logprob_f32")
-        per_kernel = {}
-        for name in (n for n in _hip.PROTOTYPES if n.endswith("_f32")):     # the workload is fp32 throughout
-            q = klib.prof_query(name)
-            if q["count"]:
-                avg_ms = q["total_ms"] / q["count"]
-                rec = {"launches_per_step": q["count"] / n_prof, "avg_us": 1e3 * avg_ms, "min_us": 1e3 * q["min_ms"],
-                       "us_per_step": 1e3 * q["total_ms"] / n_prof}
-                rec["timing"] = "HIP events, eager launches"
-                dt = dev_times.get(name)
-                if dt and not (0.4 * rec["avg_us"] <= dt["avg_us"] <= 2.5 * rec["avg_us"]):
-                    dev_times.pop(name)      # implausible against the HIP-event figure: tracer conflict, ignore
-                    dt = None
-                if dt:      # preferred: the kernel as it runs in the timed region's launch mode
-                    rec["eager_event_avg_us"] = rec["avg_us"]
-                    rec["avg_us"], rec["min_us"] = dt["avg_us"], dt["min_us"]
-                    rec["us_per_step"] = dt["avg_us"] * dt["count"] / n_dev
-                    rec["timing"] = "device timestamps, %s" % mode
-                if name in layer_bytes and rec["launches_per_step"]:
-                    # caller-side layer kernels: several launches of different shapes per step -- bytes and rate of all of them
-                    rec["role"] = "caller-side glue (the dense layers' non-GEMM backward passes), not a hot-path row"
-                    rec["algorithmic_bytes_per_step"] = layer_bytes[name]
-                    rec["GBps"] = layer_bytes[name] / (rec["us_per_step"] * 1e-6) / 1e9
-                    rec["frac_of_hbm_peak"] = rec["GBps"] / HBM_PEAK_GBS
-                if name in algo:
-                    rec["algorithmic_bytes"] = algo[name]
-                    rec["GBps"] = algo[name] / (rec["avg_us"] * 1e-6) / 1e9
-                    rec["frac_of_hbm_peak"] = rec["GBps"] / HBM_PEAK_GBS
-                    rec["working_set"] = "%.1f MB: inside the 256 MiB Infinity Cache (see hbm_resident for the same kernel " \
-                                         "beyond it)" % (algo[name] / 1e6)
-                per_kernel[name] = rec
-        # the dominant hot-path kernel of the step = the one that moves the most bytes per step (it is also the
-        # one with the most time per step; bytes are used because they do not move when a profiler is attached)
-        dominant = max((n for n in per_kernel if n in algo),
-                       key=lambda n: algo[n] * per_kernel[n]["launches_per_step"])
-        prof = klib.prof_query(dominant)
-        ev_ms = prof["total_ms"] / prof["count"]
-        if dominant in dev_times:
-            k_ms, k_min_ms, k_count = dev_times[dominant]["avg_us"] * 1e-3, dev_times[dominant]["min_us"] * 1e-3, dev_times[dominant]["count"]
-            timing = ("device start/end timestamps of each dispatch on its stream, collected in-process (torch.profiler / "
-                      "roctracer) over %d steps replayed in the timed region's launch mode (%s) right after it; HIP events "
-                      "cannot time a kernel inside a hipGraph replay, their eager-launch figure is eager_event_avg_us" % (n_dev, mode))
-        else:
-            k_ms, k_min_ms, k_count = ev_ms, prof["min_ms"], prof["count"]
-            timing = ("start/stop HIP events bound to each dispatch (hipExtLaunchKernelGGL) on the launch stream, %d steps "
-                      "of the same workload launched eagerly right after the timed region" % n_prof)
-        algo_bytes = algo[dominant]
-        achieved = algo_bytes / (k_ms * 1e-3) / 1e9
-        traffic, traffic_source = pmc_traffic(dominant, args.fused_logits, _hip.ABI_VERSION)
+        roof = None
+        if args.full:
+            # the IW kernels serve two entry points; the tracer sees kernel names only
+            if "zs_iw_reduce_f32" in dev_times and klib.prof_query("zs_iw_objective_f32")["count"] and \
+                    not klib.prof_query("zs_iw_reduce_f32")["count"]:
+                dev_times["zs_iw_objective_f32"] = dev_times.pop("zs_iw_reduce_f32")
+            # ... and so does the flat-plane sampling kernel (one draw / both draws of a latent)
+            if "zs_normal_sample_logprob_f32" in dev_times and klib.prof_query("zs_normal_sample_logprob_pair_f32")["count"] and \
+                    not klib.prof_query("zs_normal_sample_logprob_f32")["count"]:
+                dev_times["zs_normal_sample_logprob_pair_f32"] = dev_times.pop("zs_normal_sample_logprob_f32")
+            per_kernel = {}
+            for name in (n for n in _hip.PROTOTYPES if n.endswith("_f32")):     # the workload is fp32 throughout
+                q = klib.prof_query(name)
+                if q["count"]:
+                    avg_ms = q["total_ms"] / q["count"]
+                    rec = {"launches_per_step": q["count"] / n_prof, "avg_us": 1e3 * avg_ms, "min_us": 1e3 * q["min_ms"],
+                           "us_per_step": 1e3 * q["total_ms"] / n_prof}
+                    rec["timing"] = "HIP events, eager launches"
+                    dt = dev_times.get(name)
+                    if dt and not (0.4 * rec["avg_us"] <= dt["avg_us"] <= 2.5 * rec["avg_us"]):
+                        dev_times.pop(name)      # implausible against the HIP-event figure: tracer conflict, ignore
+                        dt = None
+                    if dt:      # preferred: the kernel as it runs in the timed region's launch mode
+                        rec["eager_event_avg_us"] = rec["avg_us"]
+                        rec["avg_us"], rec["min_us"] = dt["avg_us"], dt["min_us"]
+                        rec["us_per_step"] = dt["avg_us"] * dt["count"] / n_dev
+                        rec["timing"] = "device timestamps, %s" % mode
+                    if name in layer_bytes and rec["launches_per_step"]:
+                        # caller-side layer kernels: several launches of different shapes per step -- bytes and rate of all of them
+                        rec["role"] = "caller-side glue (the dense layers' non-GEMM backward passes), not a hot-path row"
+                        rec["algorithmic_bytes_per_step"] = layer_bytes[name]
+                        rec["GBps"] = layer_bytes[name] / (rec["us_per_step"] * 1e-6) / 1e9
+                        rec["frac_of_hbm_peak"] = rec["GBps"] / HBM_PEAK_GBS
+                    if name in algo:
+                        rec["algorithmic_bytes"] = algo[name]
+                        rec["GBps"] = algo[name] / (rec["avg_us"] * 1e-6) / 1e9
+                        rec["frac_of_hbm_peak"] = rec["GBps"] / HBM_PEAK_GBS
+                        rec["working_set"] = "%.1f MB: inside the 256 MiB Infinity Cache (see hbm_resident for the same kernel " \
+                                             "beyond it)" % (algo[name] / 1e6)
+                    per_kernel[name] = rec
+            # the dominant hot-path kernel of the step = the one that moves the most bytes per step (it is also the
+            # one with the most time per step; bytes are used because they do not move when a profiler is attached)
+            dominant = max((n for n in per_kernel if n in algo),
+                           key=lambda n: algo[n] * per_kernel[n]["launches_per_step"])
+            prof = klib.prof_query(dominant)
+            ev_ms = prof["total_ms"] / prof["count"]
+            if dominant in dev_times:
+                k_ms, k_min_ms, k_count = dev_times[dominant]["avg_us"] * 1e-3, dev_times[dominant]["min_us"] * 1e-3, dev_times[dominant]["count"]
+                timing = ("device start/end timestamps of each dispatch on its stream, collected in-process (torch.profiler / "
+                          "roctracer) over %d steps replayed in the timed region's launch mode (%s) right after it; HIP events "
+                          "cannot time a kernel inside a hipGraph replay, their eager-launch figure is eager_event_avg_us" % (n_dev, mode))
+            else:
+                k_ms, k_min_ms, k_count = ev_ms, prof["min_ms"], prof["count"]
+                timing = ("start/stop HIP events bound to each dispatch (hipExtLaunchKernelGGL) on the launch stream, %d steps "
+                          "of the same workload launched eagerly right after the timed region" % n_prof)
+            algo_bytes = algo[dominant]
+            achieved = algo_bytes / (k_ms * 1e-3) / 1e9
+            traffic, traffic_source = pmc_traffic(dominant, args.fused_logits, _hip.ABI_VERSION)
+            roof = {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
+                    "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_us": 1e3 * k_ms if k_ms else None,
+                    "min_launch_us": 1e3 * k_min_ms, "launches_timed": k_count, "eager_event_avg_us": 1e3 * ev_ms,
+                    "timing": "device timestamps per dispatch in the timed region's launch mode (torch.profiler / roctracer)"
+                              if dominant in dev_times else "HIP events bound to each dispatch, eager launches"}
         nbytes = sbuckets.nbytes() if staged else (obuckets.nbytes() if hooks else bucket.nbytes())
         settings = {
             "workload": "IWAE-MNIST VIMCO, batch=%d per GPU (global %d), K=%d, latent=%d, x=%d, hidden=%d, full training step "
@@ -1340,12 +1392,13 @@ def main():
             "dense_layers": DENSE_LABEL[dense],
             "mlp_gemm_library": args.blas,
             "mlp_gemm_selection": ("TunableOp (fastest fp32 solution per shape, callers' nn.Linear stack)" +
-                                   (": the picks of the parent process" if (GEMM_PICKS["loaded_from"] and world == 1) else "") +
+                                   (": the picks committed in bench_gemm_picks.csv" if GEMM_PICKS["loaded_from"] == DEFAULT_GEMM_PICKS else
+                                    ": the picks of the parent process" if (GEMM_PICKS["loaded_from"] and world == 1) else "") +
                                    ("; one tuning run for the job (rank 0's picks on every rank)" if gemm_picks_shared else "")) if tuned else "PyTorch default",
             "optimizer": "torch.optim.Adam(lr=1e-3, fused=True, capturable=True)" if args.torch_adam else "zhusuan.optim.FlatAdam(lr=1e-3)",
             "discarded_draws": "skipped (zhusuan.skip_discarded_draws)" if skip_discarded else "executed (the package default, as the reference: both draws of the latent, in one launch)",
             "launch_mode": mode,
-            "timing": "median of %d trials of %d steps, each bracketed by synchronize + barrier, max over ranks" % (len(trials), args.steps)}
+            "timing": "%d steps in one window, bracketed by synchronize + barrier, max over ranks" % args.steps}
         long_settings = {
             "dense_layers": "zhusuan.Linear / zhusuan.Sequential keep torch.nn.Linear's parameters, names and fp32 GEMMs (forward with "
                             "torch._addmm_activation: the same hipBLASLt solution with the ReLU in its epilogue); per layer one launch of this "
@@ -1361,12 +1414,6 @@ def main():
                                  "torch.optim.Adam(params, lr), PyTorch's default GEMM selection, both draws, an eager Python loop, a new "
                                  "minibatch copied in every step (iwae.py:133-160); ..._graphed is the same with zhusuan.GraphedStep "
                                  "(and capturable=True on the optimizer, which torch requires for capture) and nothing else"}
-        roof = {"bound": "hbm", "kernel": dominant, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": (achieved / HBM_PEAK_GBS) if achieved else None, "traffic": traffic,
-                "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_us": 1e3 * k_ms if k_ms else None,
-                "min_launch_us": 1e3 * k_min_ms, "launches_timed": k_count, "eager_event_avg_us": 1e3 * ev_ms,
-                "timing": "device timestamps per dispatch in the timed region's launch mode (torch.profiler / roctracer)"
-                          if dominant in dev_times else "HIP events bound to each dispatch, eager launches"}
         out = {
             "metric": baseline_metric(),
             "value": evals_per_step * world * args.steps / elapsed,
@@ -1392,19 +1439,20 @@ def main():
             "roofline": roof,
         }
         # everything that does not fit a one-line record (the driver keeps the line's scalars): per-kernel tables, trial times, prose
-        full = {"trial_ms_per_step": {"min": 1e3 * min(trials) / args.steps, "median": 1e3 * elapsed / args.steps,
-                                      "max": 1e3 * max(trials) / args.steps, "all": [1e3 * t / args.steps for t in trials]},
-                "settings_explained": long_settings, "hip_kernels": per_kernel,
-                "roofline_notes": {"timing": timing, "traffic_source": traffic_source,
-                                   "working_set": "%.0f MB per launch: resident in the 256 MiB Infinity Cache between the producer kernel and "
-                                                  "this one; hbm_resident holds the streaming kernels on working sets beyond it" % (algo_bytes / 1e6)}}
-        iw1f = per_kernel.get("zs_bernoulli_iw_objective_f32")
-        if iw1f and "frac_of_hbm_peak" in iw1f:
-            roof["iw1_fwd_frac"] = iw1f["frac_of_hbm_peak"]        # the step's forward Bernoulli stream + prior + IW objective, one launch
-        k3f = per_kernel.get("zs_bernoulli_logprob_f32") or per_kernel.get("zs_bernoulli_logits_logprob_f32")
-        if k3f and "frac_of_hbm_peak" in k3f:
-            roof["k3_fwd_frac"] = k3f["frac_of_hbm_peak"]          # (a step that runs K3 forward by itself: its in-step figure)
-        extras = world == 1 and not args.no_extras and not args.force_collective_path
+        if args.full:
+            full = {"trial_ms_per_step": {"min": 1e3 * min(trials) / args.steps, "median": 1e3 * elapsed / args.steps,
+                                          "max": 1e3 * max(trials) / args.steps, "all": [1e3 * t / args.steps for t in trials]},
+                    "settings_explained": long_settings, "hip_kernels": per_kernel,
+                    "roofline_notes": {"timing": timing, "traffic_source": traffic_source,
+                                       "working_set": "%.0f MB per launch: resident in the 256 MiB Infinity Cache between the producer kernel and "
+                                                      "this one; hbm_resident holds the streaming kernels on working sets beyond it" % (algo_bytes / 1e6)}}
+            iw1f = per_kernel.get("zs_bernoulli_iw_objective_f32")
+            if iw1f and "frac_of_hbm_peak" in iw1f:
+                roof["iw1_fwd_frac"] = iw1f["frac_of_hbm_peak"]        # the step's forward Bernoulli stream + prior + IW objective, one launch
+            k3f = per_kernel.get("zs_bernoulli_logprob_f32") or per_kernel.get("zs_bernoulli_logits_logprob_f32")
+            if k3f and "frac_of_hbm_peak" in k3f:
+                roof["k3_fwd_frac"] = k3f["frac_of_hbm_peak"]          # (a step that runs K3 forward by itself: its in-step figure)
+        extras = args.full and world == 1 and not args.no_extras and not args.force_collective_path
         if extras:
             try:
                 full["hbm_resident"] = hb = dict(k1_first, **hbm_resident_kernels(klib, dev))
@@ -1491,7 +1539,7 @@ def main():
             if "error" not in ex.get("c3_refresh", {"error": 1}):
                 # how far a new minibatch per step is from the headline (same settings, same box, same run)
                 out["extra_configs"]["c3_refresh"]["vs_headline"] = ex["c3_refresh"]["value"] / out["value"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline("c3")
             full["cpu_baseline"] = cb
             out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -1504,12 +1552,13 @@ def main():
                         c = cpu_baseline(name, budget_s=b1, one_thread_budget_s=b2, max_steps=2000, fwd_bwd_budget_s=0)
                         full["extra_configs"][name]["cpu_baseline"] = c
                         out["extra_configs"][name]["cpu_value"] = c["value"]
-        try:
-            with open(args.full_record, "w") as f:
-                json.dump(dict(out, **full), f, indent=1)
-            out["full_record"] = os.path.relpath(args.full_record, ROOT) if args.full_record.startswith(ROOT) else args.full_record
-        except OSError as e:
-            out["full_record"] = "not written: %r" % (e,)
+        if args.full:
+            try:
+                with open(args.full_record, "w") as f:
+                    json.dump(dict(out, **full), f, indent=1)
+                out["full_record"] = os.path.relpath(args.full_record, ROOT) if args.full_record.startswith(ROOT) else args.full_record
+            except OSError as e:
+                out["full_record"] = "not written: %r" % (e,)
         print(fit_line(out), flush=True)
     if wd is not None:
         wd.kick("shutdown")

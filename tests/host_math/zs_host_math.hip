@@ -1,6 +1,6 @@
 // The kernels' per-element arithmetic (csrc/zs_common.h, csrc/zs_iw_math.h: __host__ __device__) compiled for the HOST
 // and run under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_sanitizers.py):
-//     hipcc -x hip --cuda-host-only -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all ...
+//     hipcc -x hip --cuda-host-only -fno-gpu-sanitize -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all ...
 // Every function is checked against a double-precision restatement of the reference formula it implements, over edge
 // values (p in {0, 1}, sigma from 1e-6 to 1e6, uniforms at both ends of their range, |log w| ~ 550, a dominating
 // arg-max particle).  GPU sanitizers are not available on this pool, so this is where signed overflow, an invalid shift,

@@ -8,6 +8,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -58,14 +59,16 @@ def _free_port():
 
 
 def _run_bench(*extra, full=False, env=None):
+    """A `--full` run of 6 steps; `full`: return the full record as well."""
     env = dict(os.environ if env is None else env)
     env.setdefault("MASTER_ADDR", "127.0.0.1")
     env.setdefault("MASTER_PORT", "29533")
-    full_path = os.path.join(ROOT, "gpurun_out", "bench_full_test.json")
-    os.makedirs(os.path.dirname(full_path), exist_ok=True)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "3", "--full-record", full_path]
+    full_path = os.path.join(tempfile.mkdtemp(prefix="zs_bench_"), "bench_full_test.json")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "3", "--full", "--full-record", full_path]
                        + list(extra), cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    # (a C++ error prints its message ahead of a long backtrace: keep the lines that name it, not only the tail)
+    named = [l for l in r.stderr.splitlines() if "rror" in l or "what()" in l or "terminate" in l or l.startswith("bench:")]
+    assert r.returncode == 0, ("\n".join(named)[-3000:], (r.stdout + r.stderr)[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     assert len(lines[0]) <= 8192, "the one-line record must stay under 8 KB (the driver keeps a tail of stdout): %d" % len(lines[0])
@@ -160,8 +163,8 @@ def test_bench_line_single_rank():
     assert all(not isinstance(v, (dict, list)) for v in roof.values()), "roofline must hold scalars only"
     assert "workload" in rec["config"] and "model" not in rec["config"] and "test_mode" not in rec
     assert rec["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
-    # a 6-step trial is ~7 ms: the timed region is repeated until it covers at least half a second, median reported
-    assert rec["trials"] >= 3 and rec["timed_seconds_total"] >= 0.45
+    # --steps is the number of timed steps: one window of exactly 6
+    assert rec["trials"] == 1 and abs(1e3 * rec["timed_seconds_total"] - 6 * rec["ms_per_step"]) < 1e-6
     # the north-star kernel's own fraction (beyond the cache), the forward Bernoulli stream and the HBM-resident backward: flat
     for key in ("k1_frac_1M", "k1_frac_4M", "k1_frac_1M_cold", "k1_frac_4M_cold", "hbm_resident_frac", "k3_fwd_frac", "iw1_fwd_frac"):
         assert 0.2 < roof[key] <= 1.0, (key, roof.get(key))
@@ -217,6 +220,44 @@ def test_bench_line_single_rank():
     assert fx["c3_dp_step_n1"]["collective_path"].startswith("RCCL called directly")
     assert fx["c3_dp_step_n1"]["mlp_gemm_selection"].endswith("the picks of the parent process")      # the same GEMM kernels in both processes
     assert 0.8 < dp["vs_headline"] < 1.1 and 0.85 < dp["same_process_ratio"] < 1.05 and dp["extra_us_per_step"] < 60.0, dp
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_ones_outputs(tmp_path):
+    """Without --full a run sets up, warms up, times exactly --steps steps and prints the line: no roofline, extra_configs, CPU
+    baseline or full record.  --dump-outputs writes what the last timed step computed; the same arguments give the same arrays."""
+    import glob
+    dumps = []
+    for i in range(2):
+        d, full_path = tmp_path / ("out%d" % i), tmp_path / ("full%d.json" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "3",
+                            "--dump-outputs", str(d), "--full-record", str(full_path)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 6 and rec["trials"] == 1 and abs(1e3 * rec["timed_seconds_total"] - 6 * rec["ms_per_step"]) < 1e-6
+        assert rec["value"] > 1e5 and abs(rec["value"] - 256 * 50 / (rec["ms_per_step"] * 1e-3)) < 1e-3 * rec["value"]
+        assert rec["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+        assert rec["unit"] == "ELBO-evals/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+        assert rec["roofline"] is None and "extra_configs" not in rec and "cpu_baseline" not in rec and "full_record" not in rec
+        # the GEMM kernels of every run: the committed picks (per-run tuning lets near-ties come out differently)
+        assert rec["config"]["mlp_gemm_selection"].endswith("the picks committed in bench_gemm_picks.csv")
+        assert "GEMM picks committed with bench.py loaded" in r.stderr, r.stderr[-2000:]
+        assert not full_path.exists()
+        files = sorted(glob.glob(str(d / "*.npy")))
+        arrays = dict((os.path.basename(f)[:-4], np.load(f)) for f in files)
+        assert sum(os.path.getsize(f) for f in files) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert float(arrays["loss"]) == rec["final_loss"] and arrays["iw_bound"].shape == (256,)
+        params = [k for k in arrays if k.startswith("param.")]
+        assert len(params) == 14 and all(("grad." + k[6:]) in arrays for k in params)
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)
 
 
 @pytest.mark.gpu
@@ -307,7 +348,7 @@ def test_bench_two_ranks_sharing_one_gpu_over_gloo(extra):
     env = dict(os.environ)
     env["ZS_BENCH_SHARE_DEVICE"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3",
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--full",
            "--no-cpu-baseline", "--no-gemm-tuning"] + extra       # (control-flow tests: no need to tune the callers' GEMMs)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -335,7 +376,8 @@ def test_bench_two_ranks_share_one_gemm_tuning_run():
     env = dict(os.environ)
     env["ZS_BENCH_SHARE_DEVICE"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--no-cpu-baseline"]
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--full",
+           "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -353,7 +395,7 @@ def test_bench_eight_ranks_sharing_one_gpu_over_gloo():
     env = dict(os.environ)
     env["ZS_BENCH_SHARE_DEVICE"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "3",
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "3", "--full",
            "--no-cpu-baseline", "--no-gemm-tuning"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -380,7 +422,7 @@ def test_one_ranks_failed_capture_takes_every_rank_to_eager_launches_together(ex
     env["ZS_BENCH_FAIL_CAPTURE_RANK"] = "1"
     env["ZS_BENCH_WATCHDOG_S"] = "300"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3",
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "3", "--full",
            "--no-cpu-baseline", "--no-gemm-tuning"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

@@ -16,7 +16,7 @@ def test_c_oracle_under_asan_and_ubsan():
     asan_rt = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
     assert os.path.isabs(asan_rt) and os.path.exists(asan_rt), "gcc's libasan.so not found"
     env = dict(os.environ)
-    env.update({"LD_PRELOAD": asan_rt, "ZS_ORACLE_LIBRARY": lib,
+    env.update({"LD_PRELOAD": " ".join([asan_rt] + env.get("LD_PRELOAD", "").split()), "ZS_ORACLE_LIBRARY": lib,
                 # python itself "leaks" at exit; everything else is fatal
                 "ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=1",
                 "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
@@ -33,13 +33,13 @@ def test_c_oracle_under_asan_and_ubsan():
 def test_kernel_arithmetic_on_the_host_under_asan_and_ubsan(tmp_path):
     """The HIP sources' per-element helpers (Philox4x32-10, the uniform and Box-Muller conversions, the Normal / Bernoulli
     / Logistic / Uniform density terms and derivatives, the VIMCO per-particle arithmetic, the index helpers) built for the HOST with
-    `hipcc --cuda-host-only -fsanitize=address,undefined` and run: Random123 known answers, double-precision references,
+    `hipcc --cuda-host-only -fno-gpu-sanitize -fsanitize=address,undefined` and run: Random123 known answers, double-precision references,
     edge values.  (This harness found round 1's uniform reaching exactly 1.0 -- an infinite Logistic draw once in 1.7e7.)"""
     import shutil
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     exe = str(tmp_path / "zs_host_math")
     src = os.path.join(ROOT, "tests", "host_math", "zs_host_math.hip")
-    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
+    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-fno-gpu-sanitize", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", src, "-o", exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
