@@ -1,0 +1,166 @@
+// The sampler update's per-element arithmetic and indexing (csrc/zs_mcmc_math.h: __host__ __device__) compiled for the HOST and
+// run under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_mcmc_host_math.py):
+//     hipcc -x hip --cuda-host-only -Xarch_host -fsanitize=address,undefined ...
+// (1) every kind over a grid of operands -- a = 0, g = 0, large and tiny values, hyper-parameters at their extremes -- against
+// long-double restatements of the formulas of include/zs_mcmc.h, bound |err| <= 2^-20 S (float) / 2^-48 S (double), S the sum
+// of the absolute values of the terms added; (2) the element form's walk (bisection, clamping, tail) over exactly-sized heap
+// arrays for the layouts of tests/test_mcmc_kernel.py, against a plain per-tensor loop.  Prints "mcmc host math ok: N checks".
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+
+#include "../../zhusuan-pytorch_amd/csrc/zs_mcmc_math.h"
+
+static long n_checks = 0;
+static int n_fail = 0;
+static void expect(bool ok, const char* what, double got, double want) {
+  ++n_checks;
+  if (!ok) {
+    if (n_fail < 20) fprintf(stderr, "FAIL %s: got %.17g want %.17g\n", what, got, want);
+    ++n_fail;
+  }
+}
+typedef long double ld;
+template <typename T> static ld rel_bound() { return sizeof(T) == 4 ? ldexpl(1.0L, -20) : ldexpl(1.0L, -48); }
+template <typename T>
+static void near(T got, ld want, ld S, const char* what) {
+  expect(isfinite((double)got) && fabsl((ld)got - want) <= rel_bound<T>() * S, what, (double)got, (double)want);
+}
+
+struct Hyper { double lr, decay, epsilon, alpha, beta; };
+
+template <typename T>
+static void check_kinds() {
+  const double vals[] = {0.0, 1e-6, -1e-3, 0.37, -1.0, 2.5, -40.0, 1e3};
+  const double avals[] = {0.0, 1e-12, 1e-4, 0.5, 7.0, 1e4};                    // PSGLD's second moment: >= 0, exact zeros
+  const Hyper hypers[] = {{1e-3, 0.9, 1e-3, 0.25, 0.0},  {1e-2, 0.0, 1e-8, 0.3, 0.02}, {1.0, 0.999, 1.0, 1.0, 1.0},
+                          {0.0, 0.5, 1e-3, 0.0, 0.0},    {1e-6, 0.99, 0.0, 5.0, 0.0}};
+  for (const Hyper& h : hypers)
+    for (double qd : vals) for (double gd : vals) for (double zd : vals) {
+      const T q0 = (T)qd, g = (T)gd, z = (T)zd;
+      const ld Q = q0, G = g, Z = z;
+      {  // SGLD
+        const zs::McmcCoef<T> c = zs::mcmc_coef<T>(ZS_MCMC_SGLD, 0, h.lr, h.decay, h.epsilon, h.alpha, h.beta);
+        T q = q0;
+        zs::mcmc_sgld(q, g, z, c);
+        const ld t1 = 0.5L * h.lr * G, t2 = sqrtl((ld)h.lr) * Z;
+        near<T>(q, Q + t1 + t2, fabsl(Q) + fabsl(t1) + fabsl(t2), "sgld q");
+      }
+      for (double ad : avals) {  // PSGLD
+        if (h.epsilon == 0.0 && ad == 0.0 && gd == 0.0) continue;             // 1 / (0 + sqrt(0)): the caller's choice of epsilon
+        const zs::McmcCoef<T> c = zs::mcmc_coef<T>(ZS_MCMC_PSGLD, 0, h.lr, h.decay, h.epsilon, h.alpha, h.beta);
+        T q = q0, a = (T)ad;
+        const ld A0 = a;
+        zs::mcmc_psgld(q, a, g, z, c);
+        const ld ta = (ld)h.decay * A0, tb = (1.0L - (ld)h.decay) * G * G, A = ta + tb;
+        near<T>(a, A, fabsl(ta) + fabsl(tb), "psgld a");
+        if (sizeof(T) == 4 && A < 1e-30L) continue;                          // below the float range of sqrt(a'): flushed either way
+        const ld P = 1.0L / ((ld)h.epsilon + sqrtl(A)), t1 = 0.5L * h.lr * P * G, t2 = sqrtl((ld)h.lr * P) * Z;
+        near<T>(q, Q + t1 + t2, fabsl(Q) + fabsl(t1) + fabsl(t2), "psgld q");
+      }
+      for (double vd : vals) {  // SGHMC
+        const T v0 = (T)vd;
+        const ld V = v0;
+        for (int flags = 0; flags < 4; ++flags) {
+          const bool second = flags & ZS_MCMC_SECOND_ORDER, resample = flags & ZS_MCMC_RESAMPLE_V;
+          {
+            const zs::McmcCoef<T> c = zs::mcmc_coef<T>(ZS_MCMC_SGHMC_PRE, flags, h.lr, h.decay, h.epsilon, h.alpha, h.beta);
+            T q = q0, v = v0;
+            zs::mcmc_sghmc_pre(q, v, z, c);
+            const ld W = resample ? sqrtl((ld)h.lr) * Z : V;
+            near<T>(v, W, fabsl(W), "sghmc pre v");
+            near<T>(q, second ? Q + 0.5L * W : Q, fabsl(Q) + (second ? fabsl(0.5L * W) : 0.0L), "sghmc pre q");
+            if (!resample) expect(v == v0, "sghmc pre keeps v", v, v0);
+            if (!second) expect(q == q0, "sghmc pre keeps q", q, q0);
+          }
+          if (!resample) {
+            const zs::McmcCoef<T> c = zs::mcmc_coef<T>(ZS_MCMC_SGHMC_POST, flags, h.lr, h.decay, h.epsilon, h.alpha, h.beta);
+            T q = q0, v = v0;
+            zs::mcmc_sghmc_post(q, v, g, z, c);
+            const ld ns = sqrtl(2.0L * ((ld)h.alpha - (ld)h.beta) * (ld)h.lr);
+            if (second) {
+              const ld d = expl(-0.5L * (ld)h.alpha), t1 = d * d * V, t2 = d * (ld)h.lr * G, t3 = d * ns * Z, W = t1 + t2 + t3;
+              const ld S = fabsl(t1) + fabsl(t2) + fabsl(t3);
+              near<T>(v, W, S, "sghmc post2 v");
+              near<T>(q, Q + 0.5L * W, fabsl(Q) + 0.5L * S, "sghmc post2 q");
+            } else {
+              const ld t1 = (1.0L - (ld)h.alpha) * V, t2 = (ld)h.lr * G, t3 = ns * Z, W = t1 + t2 + t3;
+              const ld S = fabsl(t1) + fabsl(t2) + fabsl(t3);
+              near<T>(v, W, S, "sghmc post1 v");
+              near<T>(q, Q + W, fabsl(Q) + S, "sghmc post1 q");
+            }
+          }
+        }
+      }
+    }
+}
+
+// Host restatement of the element form's loop of k_mcmc_update (zs_mcmc.hip) for one "thread grid" of `threads` threads:
+// exactly-sized heap arrays, so that a read or write outside a tensor is an AddressSanitizer report.
+static void walk_layout(const std::vector<int64_t>& sizes, int64_t threads) {
+  const int nt = (int)sizes.size();
+  std::vector<int64_t> start(nt + 1, 0);
+  for (int s = 0; s < nt; ++s) start[s + 1] = start[s] + sizes[s];
+  const int64_t n = start[nt];
+  std::vector<std::vector<float>> q(nt), out(nt), g(nt), st(nt), z(nt), want_q(nt), want_s(nt);
+  const zs::McmcCoef<float> c = zs::mcmc_coef<float>(ZS_MCMC_PSGLD, 0, 1e-2, 0.9, 1e-3, 0.0, 0.0);
+  for (int s = 0; s < nt; ++s) {
+    q[s].resize(sizes[s]); out[s].assign(sizes[s], -777.0f); g[s].resize(sizes[s]); st[s].resize(sizes[s]); z[s].resize(sizes[s]);
+    want_q[s].resize(sizes[s]); want_s[s].resize(sizes[s]);
+    for (int64_t k = 0; k < sizes[s]; ++k) {
+      const int64_t i = start[s] + k;
+      q[s][k] = 0.001f * (float)(i % 1000) - 0.5f; g[s][k] = (float)((i * 7) % 13) - 6.0f; st[s][k] = (float)(i % 3);
+      z[s][k] = (float)((i * 5) % 11) * 0.2f - 1.0f;
+      float qq = q[s][k], aa = st[s][k];
+      zs::mcmc_psgld(qq, aa, g[s][k], z[s][k], c);
+      want_q[s][k] = qq; want_s[s][k] = aa;
+    }
+  }
+  std::vector<int> writes(n, 0);
+  const int64_t groups = (n + 3) >> 2;
+  for (int64_t t = 0; t < threads; ++t)
+    for (int64_t gi = t; gi < groups; gi += threads) {
+      float qq[4], gg[4], ss[4], zz[4];
+      int ts[4];
+      int64_t off[4];
+      for (int j = 0; j < 4; ++j) {
+        const int64_t i = zs::mcmc_clamped_index(gi, j, n);
+        expect(i >= 0 && i < n, "clamped index inside the launch", (double)i, (double)n);
+        ts[j] = zs::mcmc_tensor_of(start.data(), nt, i);
+        off[j] = i - start[ts[j]];
+        expect(ts[j] >= 0 && ts[j] < nt && off[j] >= 0 && off[j] < sizes[ts[j]], "element inside its tensor", (double)off[j], (double)ts[j]);
+        qq[j] = q[ts[j]].at(off[j]); gg[j] = g[ts[j]].at(off[j]); ss[j] = st[ts[j]].at(off[j]); zz[j] = z[ts[j]].at(off[j]);
+      }
+      for (int j = 0; j < 4; ++j) {
+        zs::mcmc_psgld(qq[j], ss[j], gg[j], zz[j], c);
+        if (zs::mcmc_element_live(gi, j, n)) {
+          out[ts[j]].at(off[j]) = qq[j];
+          st[ts[j]].at(off[j]) = ss[j];
+          ++writes[start[ts[j]] + off[j]];
+        }
+      }
+    }
+  for (int s = 0; s < nt; ++s)
+    for (int64_t k = 0; k < sizes[s]; ++k) {
+      expect(writes[start[s] + k] == 1, "every element written exactly once", writes[start[s] + k], 1);
+      expect(out[s][k] == want_q[s][k] && st[s][k] == want_s[s][k], "walk equals the per-tensor loop", out[s][k], want_q[s][k]);
+    }
+}
+
+int main() {
+  check_kinds<float>();
+  check_kinds<double>();
+  const std::vector<std::vector<int64_t>> layouts = {{1}, {3}, {4}, {5}, {5, 7}, {8, 12}, {16}, std::vector<int64_t>(32, 4),
+                                                     {1, 1, 1, 2, 9, 1}, {1048576 + 5}};
+  for (const auto& l : layouts) {
+    walk_layout(l, 3);                       // a small grid: the grid-stride loop runs many rounds
+    walk_layout(l, 256 * 1024);              // the kernel's largest grid: one round and, for the last layout, a second one with the tail
+  }
+  if (n_fail) {
+    fprintf(stderr, "%d of %ld checks FAILED\n", n_fail, n_checks);
+    return 1;
+  }
+  printf("mcmc host math ok: %ld checks\n", n_checks);
+  return 0;
+}
