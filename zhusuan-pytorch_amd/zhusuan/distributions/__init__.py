@@ -4,7 +4,8 @@
 The reference also ships Beta, Gamma, Laplace, StudentT, Poisson, Exponential (thin wrappers of
 torch.distributions, zhusuan/distributions/__init__.py:3-13): off the hot path named by BASELINE.json, kept as equally thin
 pass-throughs (``torch_families.py``: plain torch ops, no kernels) so that existing model code keeps working.  FlowDistribution
-(needs zhusuan.invertible) is not part of this build."""
+(flow_distribution.py) wraps a base distribution and a ``zhusuan.invertible`` network; its log-density tail runs on the flow
+kernels of include/zs_flow.h."""
 from .base import Distribution
 from .normal import Normal
 from .bernoulli import Bernoulli
@@ -13,5 +14,5 @@ from .uniform import Uniform
 from .torch_families import Beta, Exponential, Gamma, Laplace, Poisson, StudentT, FlowDistribution
 
 __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
-           # torch.distributions pass-throughs (no kernels) and one placeholder (FlowDistribution raises):
+           # torch.distributions pass-throughs (no kernels) and the flow-defined distribution:
            'Beta', 'Exponential', 'Gamma', 'Laplace', 'Poisson', 'StudentT', 'FlowDistribution']

@@ -6,7 +6,8 @@ is written for them and none is claimed.  They exist so that model code written 
 the switch: sampling and log-prob are exactly the reference's ``torch.distributions`` calls (on whatever device the
 parameters live on), with the reference's conventions -- parameters repeated along a leading sample axis, never
 reparameterised (``sample()``, not ``rsample()``), ``sample_cache``, the group sum of ``Distribution.log_prob``.
-One generic implementation instead of six files.  ``FlowDistribution`` needs ``zhusuan.invertible`` and stays out.
+One generic implementation instead of six files.  ``FlowDistribution`` (flow_distribution.py) lives here too: a base
+distribution seen through a ``zhusuan.invertible`` network, its log-density tail on the kernels of include/zs_flow.h.
 """
 import warnings
 
@@ -123,9 +124,114 @@ StudentT = _family('StudentT', torch.distributions.studentT.StudentT, [("df", _R
 
 
 class FlowDistribution(Distribution):
-    """Not part of the MI355X build: needs ``zhusuan.invertible`` (normalising flows, outside the hot path)."""
+    """A distribution defined by a latent (base) distribution and an invertible network
+    (zhusuan/distributions/flow_distribution.py:10-51 of the reference).
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError(
-            "zhusuan.distributions.FlowDistribution is outside the variational-inference hot path of the MI355X build "
-            "(it depends on zhusuan.invertible)")
+    ``sample(n)`` draws from ``latents`` and runs the transformation with ``reverse=True``; ``n_samples=-1`` returns
+    ``None`` (no sample: the node is only scored, as ``self.sn(flow_dis, name="x", n_samples=-1)`` does inside a
+    ``BayesianNet``).  ``log_prob(x)`` runs the transformation forward and returns ``sum_dim1 log p(z) + log_det_J``.
+
+    For a ``Normal`` or ``Logistic`` base whose parameters do not require grad and are ``[D]`` or ``[B, D]``, with a
+    log-det that is absent, a scalar or ``[B]``, the log-density, the row sum and the add are ONE launch
+    (``zs_flow_tail``; its backward another); any other base calls ``latents.log_prob``, ``torch.sum(dim=1)`` and the add as
+    the reference does.  ``zhusuan.explain`` / ``last_path`` say which ran.  A ``[B, D]`` log-det, as from a bare ``MADE``,
+    fails in the add as in the reference.
+
+    :param latents: an instance of ``Distribution``, the base of the flow.
+    :param transformation: a ``zhusuan.invertible.RevNet``; only those are supported.
+    :param flow_kwargs: additional info to be recorded.
+    """
+
+    def __init__(self, latents, transformation, flow_kwargs=None, dtype=torch.float32, group_ndims=0, device=None, **kwargs):
+        from ..invertible.base import RevNet
+        if not isinstance(transformation, RevNet) or not isinstance(latents, Distribution):
+            raise NotImplementedError(
+                "zhusuan.distributions.FlowDistribution: only a zhusuan.distributions.Distribution as `latents` and a "
+                "zhusuan.invertible.RevNet as `transformation` are supported; anything else is outside the "
+                "variational-inference hot path of the MI355X build")
+        self._latents = latents
+        self._transformation = transformation
+        self._flow_kwargs = flow_kwargs
+        self.last_path = None
+        if device is None:
+            device = latents.device
+        super(FlowDistribution, self).__init__(dtype=dtype, is_continuous=True, is_reparameterized=False,
+                                               group_ndims=group_ndims, device=device, **kwargs)
+
+    @property
+    def latents(self):
+        return self._latents
+
+    @property
+    def transformation(self):
+        return self._transformation
+
+    def _batch_shape(self):
+        return self._latents.batch_shape
+
+    def _sample(self, n_samples=-1, **kwargs):
+        if n_samples == -1:          # no sample (flow_distribution.py:43-44)
+            return None
+        z = self._latents.sample(n_samples)
+        x, _ = self._transformation.forward(z, reverse=True, **kwargs)
+        return x
+
+    def _fused_tail_operands(self, z, log_det):
+        """(base, loc, scale, param_rows, logdet, kind) when the one-launch tail takes this call, else a reason."""
+        from .normal import Normal
+        from .logistic import Logistic
+        from .. import _flow_hip
+        lat = self._latents
+        if type(lat) is Normal:
+            base, loc, scale = _flow_hip.NORMAL, lat._mean, lat.std
+        elif type(lat) is Logistic:
+            base, loc, scale = _flow_hip.LOGISTIC, lat._loc, lat._scale
+        else:
+            return "the base is a %s (the fused tail takes Normal and Logistic)" % type(lat).__name__
+        if lat.group_ndims != 0:
+            return "the base sums over group_ndims itself"
+        if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.dtype not in (torch.float32, torch.float64):
+            return "the transformed value is not a float [B, D] tensor"
+        if loc.requires_grad or scale.requires_grad:
+            return "a parameter of the base requires grad"
+        B, D = z.shape
+        if tuple(loc.shape) != tuple(scale.shape) or tuple(loc.shape) not in ((D,), (B, D)):
+            return "the base's parameters are neither [D] nor [B, D]"
+        if loc.dtype != z.dtype or loc.device != z.device or scale.device != z.device:
+            return "the base's parameters and the value differ in dtype or device"
+        if log_det is None:
+            kind = _flow_hip.LOGDET_NONE
+        elif not isinstance(log_det, torch.Tensor) or log_det.dtype != z.dtype or log_det.device != z.device:
+            return "the log-det is not a tensor of the value's dtype and device"
+        elif log_det.numel() == 1 and log_det.dim() <= 1:
+            kind = _flow_hip.LOGDET_SCALAR
+        elif tuple(log_det.shape) == (B,):
+            kind = _flow_hip.LOGDET_ROWS
+        else:
+            return "the log-det has shape %s" % (tuple(log_det.shape),)
+        return base, loc.contiguous(), scale.contiguous(), int(loc.dim() == 2), log_det, kind
+
+    def _log_prob(self, *given, **kwargs):
+        from ..utils import note_path
+        z, log_det_J = self._transformation.forward(*given, **kwargs, reverse=False)
+        plan = self._fused_tail_operands(z, log_det_J)
+        if not isinstance(plan, str):
+            from ..invertible import _functions as F
+            base, loc, scale, rows, ld, kind = plan
+            out = F.Tail.apply(z.contiguous(), loc, scale, None if ld is None else ld.contiguous(), base, rows, kind)
+            if kind == 1 and ld.dim() == 1:          # ([B] + [1] broadcasts to [B] in the reference as well)
+                out = out.reshape(torch.broadcast_shapes(out.shape, ld.shape))
+            note_path(self, "F-tail: base log-density, row sum and log-det add in one launch each way (zs_flow_tail)")
+            return out
+        note_path(self, "reference ops: latents.log_prob, torch.sum(dim=1), add", plan)
+        log_ll = torch.sum(self._latents.log_prob(z), dim=1)
+        return log_ll + log_det_J
+
+    def _log_prob_sum(self, given=None, n_fold=0):
+        x = self.sample_cache if given is None else given
+        if x is None:
+            raise RuntimeError("FlowDistribution.log_prob(None) needs a value: observe the node or pass one")
+        lp = self._log_prob(x)
+        if n_fold > 0:
+            lp = lp.sum(tuple(range(lp.dim() - n_fold, lp.dim())))
+        return lp

@@ -106,8 +106,13 @@ class ELBO(nn.Module):
     :param generator: BayesianNet p(x, z).
     :param variational: BayesianNet q(z | x).
     :param estimator: 'sgvb' (reparameterisation) or 'reinforce' (score function).
-    :param transform: normalising-flow transform of the latents -- outside the hot path of this
-        build (elbo.py:90-119 depends on zhusuan.invertible): NotImplementedError.
+    :param transform: a callable module that transforms latents of q before they reach the generator (elbo.py:90-119): it is
+        called with the tuple of the freshly drawn ``transform_var`` latents followed by ``variational.cache[k]`` for every
+        ``auxillary_var`` name, and returns ``(dict of transformed latents, log_det)``.  Typically built from
+        ``zhusuan.invertible`` layers, but any ``nn.Module`` with that signature works (planar, Householder flows).
+        With 'sgvb' the log-det enters as ``mean(sum(log_det))``; 'reinforce' drops it, as the reference does.
+    :param transform_var: names of the latents the transform replaces.
+    :param auxillary_var: names of cached values of the variational net handed to the transform as well.
     """
 
     def __init__(self, generator, variational, estimator='sgvb', transform=None, transform_var=[],
@@ -121,11 +126,12 @@ class ELBO(nn.Module):
         if estimator == 'reinforce':
             self.register_buffer('moving_mean', torch.zeros(size=[1], dtype=torch.float32))
             self.register_buffer('local_step', torch.zeros(size=[1], dtype=torch.int32))
-        if transform is not None:
-            raise NotImplementedError(
-                "ELBO(transform=...) relies on zhusuan.invertible flows, which are outside the "
-                "variational-inference hot path of the MI355X build")
-        self.transform = None
+        if transform:
+            self.transform = transform
+            self.transform_var = transform_var
+            self.auxillary_var = auxillary_var
+        else:
+            self.transform = None
         self.last_path = None          # which kernels the last evaluation ran on, and why (zhusuan.explain)
 
     def log_joint(self, nodes):
@@ -142,6 +148,8 @@ class ELBO(nn.Module):
         run_variational(self.variational, observed)
         nodes_q = self.variational.nodes
         _v_inputs = draw_latents(nodes_q)
+        if self.transform is not None:
+            return self._forward_transformed(observed, nodes_q, _v_inputs, reduce_mean, **kwargs)
         _observed = {**_v_inputs, **observed}
         self.generator(_observed)
         nodes_p = self.generator.nodes
@@ -159,6 +167,34 @@ class ELBO(nn.Module):
         logqz = self.log_joint(nodes_q)
         if self.estimator == "sgvb":
             return self.sgvb(logpxz, logqz, reduce_mean)
+        return self.reinforce(logpxz, logqz, reduce_mean, **kwargs)
+
+    def _forward_transformed(self, observed, nodes_q, drawn, reduce_mean, **kwargs):
+        """elbo.py:90-119: the named latents go through ``self.transform`` before the generator sees them; q's log-joint is
+        still that of the untransformed draws, and the transform's log-det is added by ``sgvb``.  ``drawn``: the fresh draw of
+        every latent (``draw_latents``; the reference reads ``.tensor`` of the transformed names at elbo.py:100 and of the
+        others at :114: one draw per node either way)."""
+        flow_inputs = []
+        for k in self.transform_var:
+            # only a latent variable can be transformed
+            assert k not in observed.keys()
+            assert k in nodes_q.keys()
+            flow_inputs.append(drawn[k])
+        for k in self.auxillary_var:
+            flow_inputs.append(self.variational.cache[k])
+        output, log_det = self.transform(tuple(flow_inputs))
+        # every transformed variable must be returned
+        assert len(output) == len(self.transform_var)
+        _transformed = {k: output[k] for k in self.transform_var}
+        _v_inputs = {k: v for k, v in drawn.items() if k not in _transformed}
+        _observed = {**_transformed, **_v_inputs, **observed}
+        self.generator(_observed)
+        nodes_p = self.generator.nodes
+        _note_path(self, _PATH_NODES, "a transform is set: the log-det term is not part of the one-launch log-joint (LJ1)")
+        logpxz = self.log_joint(nodes_p)
+        logqz = self.log_joint(nodes_q)
+        if self.estimator == "sgvb":
+            return self.sgvb(logpxz, logqz, reduce_mean, log_det)
         return self.reinforce(logpxz, logqz, reduce_mean, **kwargs)
 
     def _scalar_sgvb(self, nodes_p, nodes_q, why=None):
