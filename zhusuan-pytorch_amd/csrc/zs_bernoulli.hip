@@ -292,6 +292,14 @@ __global__ __launch_bounds__(256) void k_bern_logprob_serial(
 // same row mapping as the forward; reads p and x, writes gp, 16 B per lane.
 // ------------------------------------------------------------------------------------
 
+// d/dp of the row term, x ra - (1 - x) rb, with its one fused multiply-add spelled out.  Left to the compiler (bern_dp,
+// zs_common.h) the two instantiations of k_bern_logprob_bwd_rows contracted different products -- the non-temporal one
+// fma(-(1 - x), rb, x ra), the plain one fma(x, ra, -((1 - x) rb)) -- so a gradient changed in its last bits when the tensor
+// outgrew the Infinity Cache (tests/test_size_gated_variants.py, bb-K50-R33555-D40).  This is the plain instantiation's form.
+__device__ __forceinline__ float bern_dp_rows(float p, float x) {
+  return fmaf(x, rcp_fast(p + ZS_BERN_EPS), -((1.0f - x) * rcp_fast((1.0f - p) + ZS_BERN_EPS)));
+}
+
 template <bool LOGITS, bool NT>
 __global__ __launch_bounds__(256) void k_bern_logprob_bwd_rows(
     const float4* __restrict__ p, const float4* __restrict__ x, int64_t xrows,
@@ -332,15 +340,15 @@ __global__ __launch_bounds__(256) void k_bern_logprob_bwd_rows(
           if (LOGITS) {
             const float a = sigmoid_fast(pv[u].x), b = sigmoid_fast(pv[u].y), c = sigmoid_fast(pv[u].z),
                         d = sigmoid_fast(pv[u].w);
-            o.x = g * bern_dp(a, xv[u].x) * a * (1.0f - a);
-            o.y = g * bern_dp(b, xv[u].y) * b * (1.0f - b);
-            o.z = g * bern_dp(c, xv[u].z) * c * (1.0f - c);
-            o.w = g * bern_dp(d, xv[u].w) * d * (1.0f - d);
+            o.x = g * bern_dp_rows(a, xv[u].x) * a * (1.0f - a);
+            o.y = g * bern_dp_rows(b, xv[u].y) * b * (1.0f - b);
+            o.z = g * bern_dp_rows(c, xv[u].z) * c * (1.0f - c);
+            o.w = g * bern_dp_rows(d, xv[u].w) * d * (1.0f - d);
           } else {
-            o.x = g * bern_dp(pv[u].x, xv[u].x);
-            o.y = g * bern_dp(pv[u].y, xv[u].y);
-            o.z = g * bern_dp(pv[u].z, xv[u].z);
-            o.w = g * bern_dp(pv[u].w, xv[u].w);
+            o.x = g * bern_dp_rows(pv[u].x, xv[u].x);
+            o.y = g * bern_dp_rows(pv[u].y, xv[u].y);
+            o.z = g * bern_dp_rows(pv[u].z, xv[u].z);
+            o.w = g * bern_dp_rows(pv[u].w, xv[u].w);
           }
           if (NT) {   // gradient tensors beyond the Infinity Cache: streaming (non-temporal) stores
             const zs_f4v v = {o.x, o.y, o.z, o.w};
