@@ -11,13 +11,13 @@ import math
 
 import torch
 
+import host_routing
+
 NAMES = ("split", "split_bwd", "merge", "merge_bwd", "scale_fwd", "scale_bwd", "made_fwd", "made_bwd", "made_inv_col", "tail",
          "tail_bwd")
 MASK, INTERLEAVE = 0, 1
 NORMAL, LOGISTIC = 0, 1
 LOGDET_NONE, LOGDET_SCALAR, LOGDET_ROWS = 0, 1, 2
-
-_saved = None
 
 
 def _host(*tensors):
@@ -166,23 +166,8 @@ def tail_bwd(base, g, z, loc, scale, param_rows, gz, g_logdet):
             g_logdet.copy_(g)
 
 
-def install():
-    global _saved
-    from zhusuan import _flow_hip
-    if _saved is None:
-        _saved = {n: getattr(_flow_hip, n) for n in NAMES}
-    for n in NAMES:
-        setattr(_flow_hip, n, globals()[n])
-
-
-def uninstall():
-    global _saved
-    if _saved is None:
-        return
-    from zhusuan import _flow_hip
-    for n, f in _saved.items():
-        setattr(_flow_hip, n, f)
-    _saved = None
+_router = host_routing.Router("zhusuan._flow_hip", {n: globals()[n] for n in NAMES})
+install, uninstall = _router.install, _router.uninstall
 
 
 @contextlib.contextmanager
@@ -213,12 +198,4 @@ import pytest  # noqa: E402
 @pytest.fixture
 def fdev(dev):
     """The suite's ``dev`` fixture (host and hip) with the flow kernels routed accordingly: imported by the flow tests."""
-    if dev.type == "cpu":
-        install()
-        try:
-            yield dev
-        finally:
-            uninstall()
-    else:
-        uninstall()
-        yield dev
+    yield from host_routing.routed(_router, dev)

@@ -14,7 +14,8 @@ import math
 
 import torch
 
-_saved = None
+import host_routing
+
 calls = []
 
 BEGIN, STEP, END = 0, 1, 2
@@ -22,21 +23,13 @@ MAX_TENSORS, MAX_CHUNKS, TILE = 32, 16, 1024
 EPS, EPS_INIT, M, HBAR, LOG_EPS, LOG_EPSBAR, ABAR, NACC = range(8)
 
 
-def _philox(name, n, seed, call, rng_state=None):
-    import conftest
-    out = torch.empty(n, dtype=torch.float32)
-    conftest.host_kernel_library().call(name, out.data_ptr(), n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFFFFFFFFFF,
-                                        None if rng_state is None else rng_state.data_ptr(), None)
-    return out
-
-
 def philox_normal(n, seed, call, rng_state=None):
     """Elements [0, n) of the oracle's Philox normal stream (float32, CPU)."""
-    return _philox("zs_philox_normal_f32", n, seed, call, rng_state)
+    return host_routing.philox("zs_philox_normal_f32", n, seed, call, rng_state)
 
 
 def philox_uniform(n, seed, call, rng_state=None):
-    return _philox("zs_philox_uniform_f32", n, seed, call, rng_state)
+    return host_routing.philox("zs_philox_uniform_f32", n, seed, call, rng_state)
 
 
 def pieces(row):
@@ -151,21 +144,8 @@ def select(n_chains, q0, q, q_out, accept, library=None):
             o.copy_(torch.where(m, b.reshape(C, -1), a.reshape(C, -1)).reshape(o.shape))
 
 
-def install():
-    global _saved
-    from zhusuan import _hmc_hip
-    if _saved is None:
-        _saved = (_hmc_hip.move, _hmc_hip.decide, _hmc_hip.select)
-    _hmc_hip.move, _hmc_hip.decide, _hmc_hip.select = move, decide, select
-
-
-def uninstall():
-    global _saved
-    if _saved is None:
-        return
-    from zhusuan import _hmc_hip
-    _hmc_hip.move, _hmc_hip.decide, _hmc_hip.select = _saved
-    _saved = None
+_router = host_routing.Router("zhusuan._hmc_hip", {"move": move, "decide": decide, "select": select})
+install, uninstall = _router.install, _router.uninstall
 
 
 # ------------------------------------------------------------------------------------------------ the float64 truth
@@ -200,12 +180,4 @@ import pytest  # noqa: E402
 @pytest.fixture
 def hdev(dev):
     """The suite's ``dev`` fixture (host and hip) with the HMC binding routed accordingly: imported by the sampler tests."""
-    if dev.type == "cpu":
-        install()
-        try:
-            yield dev
-        finally:
-            uninstall()
-    else:
-        uninstall()
-        yield dev
+    yield from host_routing.routed(_router, dev)

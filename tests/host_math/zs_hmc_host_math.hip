@@ -156,8 +156,8 @@ static void walk_layout(int64_t C, const std::vector<int64_t>& rows) {
       const int64_t i = tile * ZS_HMC_TILE + e;
       if (i >= n) { a[e] = 0.0f; key[e] = 1 << 30; continue; }
       const int64_t gi = i >> 2;
-      const int64_t ci = zs::hmc_clamped_index(gi, (int)(i & 3), n);
-      expect(ci == i && zs::hmc_element_live(gi, (int)(i & 3), n), "a live element is its own clamped index", (double)ci, (double)i);
+      const int64_t ci = zs::flat_clamped_index(gi, (int)(i & 3), n);
+      expect(ci == i && zs::flat_element_live(gi, (int)(i & 3), n), "a live element is its own clamped index", (double)ci, (double)i);
       const zs::HmcLoc l = zs::hmc_locate(start.data(), rows.data(), nt, i);
       expect(l.s >= 0 && l.s < nt && l.off >= 0 && l.off < C * rows[l.s] && l.chain == l.off / rows[l.s] && l.chain < C &&
                  l.run_start == start[l.s] + l.chain * rows[l.s],

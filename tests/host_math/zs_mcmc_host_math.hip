@@ -125,16 +125,16 @@ static void walk_layout(const std::vector<int64_t>& sizes, int64_t threads) {
       int ts[4];
       int64_t off[4];
       for (int j = 0; j < 4; ++j) {
-        const int64_t i = zs::mcmc_clamped_index(gi, j, n);
+        const int64_t i = zs::flat_clamped_index(gi, j, n);
         expect(i >= 0 && i < n, "clamped index inside the launch", (double)i, (double)n);
-        ts[j] = zs::mcmc_tensor_of(start.data(), nt, i);
+        ts[j] = zs::flat_tensor_of(start.data(), nt, i);
         off[j] = i - start[ts[j]];
         expect(ts[j] >= 0 && ts[j] < nt && off[j] >= 0 && off[j] < sizes[ts[j]], "element inside its tensor", (double)off[j], (double)ts[j]);
         qq[j] = q[ts[j]].at(off[j]); gg[j] = g[ts[j]].at(off[j]); ss[j] = st[ts[j]].at(off[j]); zz[j] = z[ts[j]].at(off[j]);
       }
       for (int j = 0; j < 4; ++j) {
         zs::mcmc_psgld(qq[j], ss[j], gg[j], zz[j], c);
-        if (zs::mcmc_element_live(gi, j, n)) {
+        if (zs::flat_element_live(gi, j, n)) {
           out[ts[j]].at(off[j]) = qq[j];
           st[ts[j]].at(off[j]) = ss[j];
           ++writes[start[ts[j]] + off[j]];

@@ -10,7 +10,8 @@ import math
 
 import torch
 
-_saved = None
+import host_routing
+
 calls = []
 
 SGLD, PSGLD, SGHMC_PRE, SGHMC_POST = 0, 1, 2, 3
@@ -20,11 +21,7 @@ MAX_TENSORS = 32
 
 def philox_normal(n, seed, call, rng_state=None):
     """Elements [0, n) of the oracle's Philox normal stream (float32, CPU)."""
-    import conftest
-    out = torch.empty(n, dtype=torch.float32)
-    conftest.host_kernel_library().call("zs_philox_normal_f32", out.data_ptr(), n, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                        int(call) & 0xFFFFFFFFFFFFFFFF, None if rng_state is None else rng_state.data_ptr(), None)
-    return out
+    return host_routing.philox("zs_philox_normal_f32", n, seed, call, rng_state)
 
 
 def update(kind, q_in, q_out, grad=None, state=None, z=None, lr=0., decay=0., epsilon=0., alpha=0., beta=0., flags=0,
@@ -81,21 +78,8 @@ def update(kind, q_in, q_out, grad=None, state=None, z=None, lr=0., decay=0., ep
             start += sizes[i]
 
 
-def install():
-    global _saved
-    from zhusuan import _mcmc_hip
-    if _saved is None:
-        _saved = _mcmc_hip.update
-    _mcmc_hip.update = update
-
-
-def uninstall():
-    global _saved
-    if _saved is None:
-        return
-    from zhusuan import _mcmc_hip
-    _mcmc_hip.update = _saved
-    _saved = None
+_router = host_routing.Router("zhusuan._mcmc_hip", {"update": update})
+install, uninstall = _router.install, _router.uninstall
 
 
 import pytest  # noqa: E402
@@ -104,12 +88,4 @@ import pytest  # noqa: E402
 @pytest.fixture
 def mdev(dev):
     """The suite's ``dev`` fixture (host and hip) with the samplers' update routed accordingly: imported by the sampler tests."""
-    if dev.type == "cpu":
-        install()
-        try:
-            yield dev
-        finally:
-            uninstall()
-    else:
-        uninstall()
-        yield dev
+    yield from host_routing.routed(_router, dev)

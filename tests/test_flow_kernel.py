@@ -36,7 +36,7 @@ DTYPES = [pytest.param(torch.float32, id="f32"), pytest.param(torch.float64, id=
 @pytest.fixture(scope="module")
 def lib():
     from zhusuan import _flow_hip
-    return _flow_hip.FlowLibrary(_flow_hip.LIB_PATH)
+    return _flow_hip.lib(_flow_hip.LIB_PATH)
 
 
 def sfx(dtype):

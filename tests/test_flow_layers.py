@@ -439,7 +439,7 @@ def test_a_host_tensor_raises_on_the_hip_back_end():
 def test_missing_library_error():
     from zhusuan import _flow_hip
     with pytest.raises(RuntimeError, match="make -C zhusuan-pytorch_amd/csrc flow"):
-        _flow_hip.FlowLibrary("/nonexistent/libzs_flow.so")
+        _flow_hip.lib("/nonexistent/libzs_flow.so")
     with pytest.raises(RuntimeError, match="There is no CPU fallback"):
         _flow_hip.lib(path="/nonexistent/libzs_flow.so")
 

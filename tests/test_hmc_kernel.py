@@ -5,6 +5,8 @@ element is held to |err| <= 2^-20 S for _f32 (2^-48 S for _f64), S the sum of th
 kinetic sum over n terms to (n 2^-24 + 2^-20) sum_i S_i (n 2^-53 + 2^-48 for _f64), S_i the bound's S of term i.  Every layout
 runs with aligned operands (the 16-byte path where starts and rows allow it) and with every operand shifted by one element
 (the element path): the two must agree bit for bit, and sentinel elements around every output must survive."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -25,7 +27,7 @@ F32, F64 = torch.float32, torch.float64
 @pytest.fixture(scope="module")
 def lib():
     from zhusuan import _hmc_hip
-    return _hmc_hip.HmcLibrary(_hmc_hip.LIB_PATH)
+    return _hmc_hip.lib(_hmc_hip.LIB_PATH)
 
 
 def _ptr(t):
@@ -481,4 +483,7 @@ def test_rejected_arguments_and_empty_launches_write_nothing(lib):
     torch.cuda.synchronize()
     assert all(bool((x == SENTINEL).all()) for x in t.values()) and bool((out == SENTINEL).all()) and bool((acc == 777).all())
     assert torch.equal(st.cpu(), state_block().cpu()), "a rejected or empty call wrote something"
-    assert lib.ksum_slots([1, 1024, 1025, 1026]) == 1 + 2 + 2 + 3 and lib.ksum_slots([5, 0]) == -1
+
+    def ksum_slots(rows):          # the C entry's own count (the binding's ksum_slots() is its Python restatement)
+        return lib.raw("zs_hmc_ksum_slots", (ctypes.c_int64 * len(rows))(*rows), len(rows))
+    assert ksum_slots([1, 1024, 1025, 1026]) == 1 + 2 + 2 + 3 and ksum_slots([5, 0]) == -1

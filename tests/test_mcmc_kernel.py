@@ -27,7 +27,7 @@ SENTINEL = 777.0
 @pytest.fixture(scope="module")
 def lib():
     from zhusuan import _mcmc_hip
-    return _mcmc_hip.McmcLibrary(_mcmc_hip.LIB_PATH)
+    return _mcmc_hip.lib(_mcmc_hip.LIB_PATH)
 
 
 def _ptr(t):

@@ -357,7 +357,7 @@ def test_mcmc_update_noise_over_the_id_matrix(sizes):
     (test_mcmc_kernel.py): z is read back as v / c.  Flat element start + i of the launch's stream (include/zs_mcmc.h)."""
     import test_mcmc_kernel as MK
     from zhusuan import _mcmc_hip
-    lib = _mcmc_hip.McmcLibrary(_mcmc_hip.LIB_PATH)
+    lib = _mcmc_hip.lib(_mcmc_hip.LIB_PATH)
     n = sum(sizes)
     q, g, s, _ = MK.inputs(n, torch.float32, 7)
     c = float(torch.tensor(np.sqrt(MK.HYPER["lr"]), dtype=torch.float64).to(torch.float32))
@@ -375,7 +375,7 @@ def test_hmc_momenta_over_the_id_matrix(C, rows, shift):
     """zs_hmc_move_f32 / _f64 BEGIN returns the momentum it drew in p0 (test_hmc_kernel.py)."""
     import test_hmc_kernel as HK
     from zhusuan import _hmc_hip
-    lib = _hmc_hip.HmcLibrary(_hmc_hip.LIB_PATH)
+    lib = _hmc_hip.lib(_hmc_hip.LIB_PATH)
     n = C * sum(rows)
     for dtype in (HK.F32, HK.F64):
         q, p, g, _ = HK.inputs(n, dtype, 7)
@@ -395,7 +395,7 @@ def test_hmc_decide_uniforms_over_the_id_matrix(C):
     uniforms (exact in fp32), as test_hmc_kernel.py compares it with the main library's stream."""
     import test_hmc_kernel as HK
     from zhusuan import _hmc_hip
-    lib = _hmc_hip.HmcLibrary(_hmc_hip.LIB_PATH)
+    lib = _hmc_hip.lib(_hmc_hip.LIB_PATH)
     k, l0, l1, _ = HK.decide_inputs(C, 5)
     for ident in SAMPLER_IDS:
         kw = ident.kw(HK.DEV)

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "zs_flow_math.h"
+#include "zs_flat_math.h"          // Vec4
 #include "../../include/zs_hip.h"
 #include "../../include/zs_flow.h"
 
@@ -33,9 +34,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr unsigned kMaxGrid = 2048;
-
-template <typename T>
-struct alignas(16) Vec4 { T v[4]; };
 
 template <typename T, int W>
 __device__ __forceinline__ void ld(const T* p, int64_t i, T (&r)[W]) {

@@ -28,9 +28,6 @@ constexpr int DECIDE_THREADS = 1024;
 constexpr int DEAD_KEY = 1 << 30;
 
 template <typename T>
-struct alignas(16) Vec4 { T v[4]; };
-
-template <typename T>
 struct Table {
   const T* q0[ZS_HMC_MAX_TENSORS];
   T* q[ZS_HMC_MAX_TENSORS];
@@ -102,11 +99,11 @@ __global__ __launch_bounds__(THREADS) void k_hmc_move(const Table<T> ts, int64_t
         bool inj[4], all_inj = true;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const int64_t i = hmc_clamped_index(gi, j, n);
+          const int64_t i = flat_clamped_index(gi, j, n);
           const HmcLoc l = hmc_locate(ts.start, ts.row, ts.n_tensors, i);
           sj[j] = l.s;
           off[j] = l.off;
-          if (hmc_element_live(gi, j, n)) key[j] = hmc_key(l.run_start, tile);
+          if (flat_element_live(gi, j, n)) key[j] = hmc_key(l.run_start, tile);
           g[j] = ts.grad[l.s][l.off];
           inj[j] = (ts.has_z >> l.s) & 1u;
           all_inj = all_inj && inj[j];
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(THREADS) void k_hmc_move(const Table<T> ts, int64_t
           if (KIND == ZS_HMC_BEGIN) t = hmc_begin(q[j], g[j], zz[j], st, q[j], p[j]);
           else if (KIND == ZS_HMC_STEP) { hmc_step(q[j], p[j], g[j], st); t = (T)0; }
           else t = hmc_end(p[j], g[j], st);
-          if (hmc_element_live(gi, j, n)) {
+          if (flat_element_live(gi, j, n)) {
             sq[j] = t;
             if (KIND != ZS_HMC_END) {
               ts.q[sj[j]][off[j]] = q[j];
@@ -191,7 +188,7 @@ __global__ __launch_bounds__(THREADS) void k_hmc_select(const Table<T> ts, int64
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (!hmc_element_live(gi, j, n)) continue;
+        if (!flat_element_live(gi, j, n)) continue;
         const HmcLoc l = hmc_locate(ts.start, ts.row, ts.n_tensors, (gi << 2) + j);
         ts.p0[l.s][l.off] = accept[l.chain] ? ts.q[l.s][l.off] : ts.q0[l.s][l.off];
       }

@@ -5,12 +5,10 @@
 #pragma once
 #include <math.h>
 #include "zs_common.h"
+#include "zs_flat_math.h"          // flat_fma, flat_tensor_of and the element form's walk (flat_clamped_index, flat_element_live)
 #include "../../include/zs_hmc.h"
 
 namespace zs {
-
-ZS_HD float hmc_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-ZS_HD double hmc_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // eps is held in double; the element arithmetic uses it, and eps/2, rounded to T
 template <typename T>
@@ -26,20 +24,20 @@ ZS_HD HmcStep<T> hmc_step_of(double eps) {
 // BEGIN   p0 = z;  p = p0 + (eps/2) g;  q = q0 + eps p;  returns p0^2 (the kinetic term, in T)
 template <typename T>
 ZS_HD T hmc_begin(T q0, T g, T z, const HmcStep<T>& s, T& q, T& p) {
-  p = hmc_fma(s.half, g, z);
-  q = hmc_fma(s.eps, p, q0);
+  p = flat_fma(s.half, g, z);
+  q = flat_fma(s.eps, p, q0);
   return z * z;
 }
 // STEP    p = p + eps g;  q = q + eps p
 template <typename T>
 ZS_HD void hmc_step(T& q, T& p, T g, const HmcStep<T>& s) {
-  p = hmc_fma(s.eps, g, p);
-  q = hmc_fma(s.eps, p, q);
+  p = flat_fma(s.eps, g, p);
+  q = flat_fma(s.eps, p, q);
 }
 // END     pL = p + (eps/2) g;  returns pL^2
 template <typename T>
 ZS_HD T hmc_end(T p, T g, const HmcStep<T>& s) {
-  const T pl = hmc_fma(s.half, g, p);
+  const T pl = flat_fma(s.half, g, p);
   return pl * pl;
 }
 
@@ -71,16 +69,6 @@ ZS_HD void hmc_adapt(double* st, double abar, int adapting, double delta, double
 }
 
 // ---------------------------------------------------------------- index maps
-// tensor of flat element i: the last s with start[s] <= i (start[0] = 0, ascending)
-ZS_HD int hmc_tensor_of(const int64_t* start, int n_tensors, int64_t i) {
-  int lo = 0, hi = n_tensors - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (start[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // where flat element i lives: its tensor, its chain, and the flat index at which that chain's row of that tensor begins
 struct HmcLoc {
   int s;
@@ -88,7 +76,7 @@ struct HmcLoc {
 };
 ZS_HD HmcLoc hmc_locate(const int64_t* start, const int64_t* row, int n_tensors, int64_t i) {
   HmcLoc l;
-  l.s = hmc_tensor_of(start, n_tensors, i);
+  l.s = flat_tensor_of(start, n_tensors, i);
   l.off = i - start[l.s];
   int64_t r;
   divmod(l.off, row[l.s], l.chain, r);
@@ -111,14 +99,5 @@ ZS_HD int hmc_key(int64_t run_start, int64_t tile) {
 ZS_HD int64_t hmc_slot(int64_t chain, int64_t slots, int64_t poff, int64_t run_start, int64_t tile) {
   return chain * slots + poff + (tile - run_start / ZS_HMC_TILE);
 }
-
-// The element form's walk over one group of four (as zs_mcmc_math.h): element j of group gi is flat index 4 gi + j when that
-// is below n, else (clamped: the loads stay unconditional, the store is dropped) the group's first element.
-ZS_HD int64_t hmc_clamped_index(int64_t gi, int j, int64_t n) {
-  const int64_t i0 = gi << 2;
-  const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-  return i0 + (j < cnt ? j : 0);
-}
-ZS_HD bool hmc_element_live(int64_t gi, int j, int64_t n) { return (gi << 2) + j < n; }
 
 }  // namespace zs

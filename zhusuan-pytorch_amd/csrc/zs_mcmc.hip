@@ -23,9 +23,6 @@ using namespace zs;
 namespace {
 
 template <typename T>
-struct alignas(16) Vec4 { T v[4]; };
-
-template <typename T>
 struct Table {
   const T* q_in[ZS_MCMC_MAX_TENSORS];
   T* q_out[ZS_MCMC_MAX_TENSORS];
@@ -51,7 +48,7 @@ __global__ __launch_bounds__(1024) void k_mcmc_update(const Table<T> ts, const M
     if (VEC) {
       // every tensor starts at a multiple of 4 and is aligned for one wide access per operand (checked on the host)
       const int64_t i0 = gi << 2;
-      const int s = mcmc_tensor_of(ts.start, ts.n_tensors, i0);
+      const int s = flat_tensor_of(ts.start, ts.n_tensors, i0);
       const int64_t off = i0 - ts.start[s];
       const bool inj = (ts.has_z >> s) & 1u;
       Vec4<T> q = *reinterpret_cast<const Vec4<T>*>(ts.q_in[s] + off), g, st, zz;
@@ -82,8 +79,8 @@ __global__ __launch_bounds__(1024) void k_mcmc_update(const Table<T> ts, const M
       bool inj[4], all_inj = true;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int64_t i = mcmc_clamped_index(gi, j, n);
-        const int s = mcmc_tensor_of(ts.start, ts.n_tensors, i);
+        const int64_t i = flat_clamped_index(gi, j, n);
+        const int s = flat_tensor_of(ts.start, ts.n_tensors, i);
         const int64_t off = i - ts.start[s];
         inj[j] = (ts.has_z >> s) & 1u;
         all_inj = all_inj && inj[j];
@@ -103,7 +100,7 @@ __global__ __launch_bounds__(1024) void k_mcmc_update(const Table<T> ts, const M
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         mcmc_apply<T, KIND>(q[j], st[j], g[j], zz[j], c);
-        if (mcmc_element_live(gi, j, n)) {
+        if (flat_element_live(gi, j, n)) {
           *qd[j] = q[j];
           if (STATE) *sd[j] = st[j];
         }

@@ -6,12 +6,11 @@
 #pragma once
 #include <math.h>
 #include "zs_common.h"
+#include "zs_flat_math.h"          // flat_fma and the flat index maps (flat_tensor_of, flat_clamped_index, flat_element_live)
 #include "../../include/zs_mcmc.h"
 
 namespace zs {
 
-ZS_HD float mcmc_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-ZS_HD double mcmc_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 ZS_HD float mcmc_sqrt(float x) { return sqrt_fast(x); }        // v_sqrt_f32, 1 ulp
 ZS_HD double mcmc_sqrt(double x) { return __builtin_sqrt(x); }
 ZS_HD float mcmc_rcp(float x) { return rcp_fast(x); }          // v_rcp_f32, 1 ulp
@@ -47,32 +46,32 @@ __host__ inline McmcCoef<T> mcmc_coef(int kind, int flags, double lr, double dec
 // SGLD.py:50-52   q' = q + (lr/2) g + sqrt(lr) z
 template <typename T>
 ZS_HD void mcmc_sgld(T& q, T g, T z, const McmcCoef<T>& c) {
-  q = mcmc_fma(c.sqrt_lr, z, mcmc_fma(c.half_lr, g, q));
+  q = flat_fma(c.sqrt_lr, z, flat_fma(c.half_lr, g, q));
 }
 
 // SGLD.py:77-80   a' = decay a + (1 - decay) g^2;  G = 1 / (epsilon + sqrt(a'));  q' = q + (lr/2) G g + sqrt(lr G) z
 template <typename T>
 ZS_HD void mcmc_psgld(T& q, T& a, T g, T z, const McmcCoef<T>& c) {
-  a = mcmc_fma(c.decay, a, c.one_minus_decay * (g * g));
+  a = flat_fma(c.decay, a, c.one_minus_decay * (g * g));
   const T G = mcmc_rcp(c.epsilon + mcmc_sqrt(a));
-  q = mcmc_fma(mcmc_sqrt(c.lr * G), z, mcmc_fma(c.half_lr * G, g, q));
+  q = flat_fma(mcmc_sqrt(c.lr * G), z, flat_fma(c.half_lr * G, g, q));
 }
 
 // SGHMC.py:26-27,32-33,35-36 (before the gradient)   v' = resample_v ? sqrt(lr) z : v;  q' = second_order ? q + v'/2 : q
 template <typename T>
 ZS_HD void mcmc_sghmc_pre(T& q, T& v, T z, const McmcCoef<T>& c) {
   if (c.resample_v) v = c.sqrt_lr * z;
-  if (c.second_order) q = mcmc_fma((T)0.5, v, q);
+  if (c.second_order) q = flat_fma((T)0.5, v, q);
 }
 
 // SGHMC.py:47-48   v' = (1 - alpha) v + lr g + noise z;  q' = q + v'
 // SGHMC.py:52-54   v' = d (d v + lr g + noise z);  q' = q + v'/2        (d = exp(-alpha/2))
 template <typename T>
 ZS_HD void mcmc_sghmc_post(T& q, T& v, T g, T z, const McmcCoef<T>& c) {
-  const T t = mcmc_fma(c.noise, z, mcmc_fma(c.lr, g, c.damp * v));
+  const T t = flat_fma(c.noise, z, flat_fma(c.lr, g, c.damp * v));
   if (c.second_order) {
     v = c.damp * t;
-    q = mcmc_fma((T)0.5, v, q);
+    q = flat_fma((T)0.5, v, q);
   } else {
     v = t;
     q = q + v;
@@ -91,24 +90,5 @@ ZS_HD void mcmc_apply(T& q, T& s, T g, T z, const McmcCoef<T>& c) {
 ZS_HD bool mcmc_reads_grad(int kind) { return kind != ZS_MCMC_SGHMC_PRE; }
 ZS_HD bool mcmc_has_state(int kind) { return kind != ZS_MCMC_SGLD; }
 ZS_HD bool mcmc_draws(int kind, int flags) { return kind != ZS_MCMC_SGHMC_PRE || (flags & ZS_MCMC_RESAMPLE_V); }
-
-// tensor of flat element i: the last s with start[s] <= i (start[0] = 0, ascending)
-ZS_HD int mcmc_tensor_of(const int64_t* start, int n_tensors, int64_t i) {
-  int lo = 0, hi = n_tensors - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (start[mid] <= i) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// The element form's walk over one group of four: element j of group gi is flat index 4 gi + j when that is below n,
-// else (clamped: the loads stay unconditional, the store is dropped) the group's first element.
-ZS_HD int64_t mcmc_clamped_index(int64_t gi, int j, int64_t n) {
-  const int64_t i0 = gi << 2;
-  const int cnt = n - i0 < 4 ? (int)(n - i0) : 4;
-  return i0 + (j < cnt ? j : 0);
-}
-ZS_HD bool mcmc_element_live(int64_t gi, int j, int64_t n) { return (gi << 2) + j < n; }
 
 }  // namespace zs

@@ -11,9 +11,7 @@ the caller hands in contiguous operands and the outputs to fill.
 import ctypes
 import os
 
-import torch
-
-from . import _hip
+from . import _binding, _hip
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libzs_flow.so")
@@ -29,7 +27,7 @@ _i = ctypes.c_int
 _n = ctypes.c_int64
 
 # name -> argument types (without the _f32 / _f64 suffix), in the order of include/zs_flow.h
-_PROTOTYPES = {
+_PROTOTYPES = _binding.both({
     "zs_flow_split": [_i, _p, _p, _p, _n, _n, _i, _p],
     "zs_flow_split_bwd": [_i, _p, _p, _p, _n, _n, _i, _p],
     "zs_flow_merge": [_i, _p, _p, _p, _d, _p, _n, _n, _i, _p],
@@ -41,56 +39,25 @@ _PROTOTYPES = {
     "zs_flow_made_inv_col": [_p, _p, _p, _n, _n, _n, _p],
     "zs_flow_tail": [_i, _p, _p, _p, _i, _p, _i, _p, _n, _n, _p],
     "zs_flow_tail_bwd": [_i, _p, _p, _p, _p, _i, _p, _p, _n, _n, _p],
-}
-_ERRORS = {-1: "invalid argument (ZS_EINVAL)", -2: "not supported (ZS_ENOTSUP)"}
-
-
-class FlowLibrary(object):
-    """A loaded shared object exporting the zs_flow_* C ABI (binding the symbols needs no GPU)."""
-
-    def __init__(self, path=None):
-        path = path or LIB_PATH
-        if not os.path.exists(path):
-            raise RuntimeError(
-                "zhusuan.invertible (MI355X build): flow kernel library not found at %s -- run "
-                "`make -C zhusuan-pytorch_amd/csrc flow` (or `python -c 'import __graft_entry__ as g; g.build()'`). "
-                "There is no CPU fallback." % path)
-        self.path = path
-        self.cdll = ctypes.CDLL(path)
-        self.cdll.zs_flow_abi_version.restype = ctypes.c_int
-        self.cdll.zs_flow_abi_version.argtypes = []
-        got = self.cdll.zs_flow_abi_version()
-        if got != ABI_VERSION:
-            raise RuntimeError("zhusuan.invertible: %s has ABI version %d, expected %d" % (path, got, ABI_VERSION))
-        self._fn = {}
-        for base, argtypes in _PROTOTYPES.items():
-            for sfx in ("_f32", "_f64"):
-                fn = getattr(self.cdll, base + sfx)
-                fn.restype = ctypes.c_int
-                fn.argtypes = argtypes
-                self._fn[base + sfx] = fn
-
-    def raw(self, name, *args):
-        """The entry point's own return code (0 = ok)."""
-        return self._fn[name](*args)
-
-    def call(self, name, *args):
-        rc = self._fn[name](*args)
-        if rc != 0:
-            raise RuntimeError("%s failed with code %d: %s" % (name, rc, _ERRORS.get(rc, "HIP error")))
-
+})
 
 _LIB = None
 
 
+def FlowLibrary(path):
+    """A freshly loaded, uncached ``_binding.Library`` of the zs_flow_* C ABI from the file at ``path``; ``lib()`` keeps the
+    in-tree one."""
+    return _binding.Library(path, who="zhusuan.invertible", what="flow kernel library", make_target="flow",
+                            abi_symbol="zs_flow_abi_version", abi_version=ABI_VERSION, prototypes=_PROTOTYPES)
+
+
 def lib(path=None):
     """The flow library (lazy); ``path`` loads another file instead of the in-tree one and does not replace it."""
-    global _LIB
-    if path is not None:
-        return FlowLibrary(path)
-    if _LIB is None:
-        _LIB = FlowLibrary(LIB_PATH)
-    return _LIB
+    return _binding.lazy_lib(globals(), FlowLibrary, path)
+
+
+def _suffix(dtype):
+    return _binding.suffix(dtype, "zhusuan.invertible: tensors must be float32 or float64, got %s")
 
 
 def check_dtype(*tensors):
@@ -99,8 +66,7 @@ def check_dtype(*tensors):
     for t in tensors:
         if t is None:
             continue
-        if t.dtype not in (torch.float32, torch.float64):
-            raise RuntimeError("zhusuan.invertible: tensors must be float32 or float64, got %s" % t.dtype)
+        _suffix(t.dtype)
         if dt is None:
             dt = t.dtype
         elif t.dtype != dt:
@@ -115,7 +81,7 @@ def _call(base, first, tensors, *args):
         if t is not None and not t.is_contiguous():
             raise RuntimeError("zhusuan.invertible: kernel operands must be contiguous")
     _hip.require_device(*tensors)
-    lib().call(base + ("_f32" if dt == torch.float32 else "_f64"), *(args + (_hip.stream_for(first),)))
+    lib().call(base + _suffix(dt), *(args + (_hip.stream_for(first),)))
 
 
 def _bd(t):

@@ -12,6 +12,8 @@ import os
 
 import torch
 
+from . import _binding
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The in-tree library.  ZS_HIP_LIBRARY points at an alternative build of the same ABI (kernel experiments: tools/); bench.py
 # records which file was loaded (path, sha256, zs_build_info) and refuses an override unless --allow-experiments is given.
@@ -122,40 +124,29 @@ PROTOTYPES.update({
 PROTOTYPES.update({name[:-4] + "_f64": args for name, args in list(PROTOTYPES.items())})
 
 
-class KernelLibrary(object):
+# what the library exports besides its compute entry points: symbol -> (restype, argtypes)
+_SERVICE = {
+    "zs_error_string": (ctypes.c_char_p, [_int]),
+    "zs_build_info": (ctypes.c_char_p, []),
+    "zs_normal_sample_pair_one_launch": (_int, [_i64, _i64, _i64, _int]),
+    "zs_prof_enable": (_int, [_int]),
+    "zs_prof_kernel_id": (_int, [ctypes.c_char_p]),
+    "zs_prof_query": (_int, [_int] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(_i64)]),
+}
+
+
+class KernelLibrary(_binding.Library):
     """A loaded shared object exporting the zs_* C ABI."""
 
     def __init__(self, path):
-        if not os.path.exists(path):
-            raise RuntimeError(
-                "zhusuan (MI355X build): kernel library not found at %s -- run "
-                "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C zhusuan-pytorch_amd/csrc`). "
-                "There is no CPU fallback." % path)
-        self.path = path
-        self.cdll = ctypes.CDLL(path)
-        self.cdll.zs_abi_version.restype = _int
-        self.cdll.zs_abi_version.argtypes = []
-        self.cdll.zs_error_string.restype = ctypes.c_char_p
-        self.cdll.zs_error_string.argtypes = [_int]
-        self.cdll.zs_build_info.restype = ctypes.c_char_p
-        self.cdll.zs_build_info.argtypes = []
-        got = self.cdll.zs_abi_version()
-        if got != ABI_VERSION:
-            raise RuntimeError("zhusuan: %s has ABI version %d, expected %d" % (path, got, ABI_VERSION))
-        self._fn = {}
-        for name, argtypes in PROTOTYPES.items():
-            fn = getattr(self.cdll, name)  # AttributeError if a symbol is missing
-            fn.restype = _int
-            fn.argtypes = argtypes
-            self._fn[name] = fn
-        self.cdll.zs_normal_sample_pair_one_launch.restype = _int
-        self.cdll.zs_normal_sample_pair_one_launch.argtypes = [_i64, _i64, _i64, _int]
-        self.cdll.zs_prof_enable.restype = _int
-        self.cdll.zs_prof_enable.argtypes = [_int]
-        self.cdll.zs_prof_kernel_id.restype = _int
-        self.cdll.zs_prof_kernel_id.argtypes = [ctypes.c_char_p]
-        self.cdll.zs_prof_query.restype = _int
-        self.cdll.zs_prof_query.argtypes = [_int] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(_i64)]
+        super().__init__(path, who="zhusuan", abi_symbol="zs_abi_version", abi_version=ABI_VERSION, prototypes=PROTOTYPES,
+                         build_hint="`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C zhusuan-pytorch_amd/csrc`)")
+        for name, proto in _SERVICE.items():          # reached through self.cdll by the methods below, not through call()
+            self.bind(name, proto)
+
+    def _error_text(self, rc):
+        msg = self.cdll.zs_error_string(rc)
+        return msg.decode() if msg else "?"
 
     def build_info(self):
         """The library's own one-line description (target, ABI, release / experiments build)."""
@@ -197,12 +188,6 @@ class KernelLibrary(object):
     def pair_draw_is_one_launch(self, K, M, D):
         """Whether two draws of a latent ([K, M] each, rows of D) fit ONE launch of the sampling kernel (zs_normal_sample_logprob_pair)."""
         return self.cdll.zs_normal_sample_pair_one_launch(K, M, D, 1) == 1
-
-    def call(self, name, *args):
-        rc = self._fn[name](*args)
-        if rc != 0:
-            msg = self.cdll.zs_error_string(rc)
-            raise RuntimeError("%s failed with code %d: %s" % (name, rc, msg.decode() if msg else "?"))
 
 
 _LIB = None          # the HIP library (lazy)

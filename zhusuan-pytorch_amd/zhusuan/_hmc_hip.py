@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from . import _hip
+from . import _binding, _hip
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libzs_hmc.so")
@@ -40,72 +40,30 @@ class HmcChunk(ctypes.Structure):           # struct zs_hmc_chunk
     _fields_ = [("k0", _p), ("k1", _p), ("slots", _i64), ("is_f64", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
-_MOVE_ARGS = [ctypes.c_int, _p, ctypes.c_int, _i64, _i64, _p, _p, _u64, _u64, _p, _p]
-_DECIDE_ARGS = [_p, ctypes.c_int, _i64, _p, _p, _p, _p, _p, _p, ctypes.c_int, _d, _d, _d, _d, _u64, _u64, _p, _p]
-_SELECT_ARGS = [_p, ctypes.c_int, _i64, _i64, _p, _p]
-_ERRORS = {-1: "invalid argument (ZS_EINVAL)", -2: "not supported (ZS_ENOTSUP)"}
-
-
-class HmcLibrary(object):
-    """A loaded shared object exporting the zs_hmc_* C ABI (binding the symbols needs no GPU)."""
-
-    def __init__(self, path=None):
-        path = path or LIB_PATH
-        if not os.path.exists(path):
-            raise RuntimeError(
-                "zhusuan.mcmc.HMC (MI355X build): kernel library not found at %s -- run "
-                "`make -C zhusuan-pytorch_amd/csrc hmc` (or `python -c 'import __graft_entry__ as g; g.build()'`). "
-                "There is no CPU fallback." % path)
-        self.path = path
-        self.cdll = ctypes.CDLL(path)
-        self.cdll.zs_hmc_abi_version.restype = ctypes.c_int
-        self.cdll.zs_hmc_abi_version.argtypes = []
-        got = self.cdll.zs_hmc_abi_version()
-        if got != ABI_VERSION:
-            raise RuntimeError("zhusuan.mcmc.HMC: %s has ABI version %d, expected %d" % (path, got, ABI_VERSION))
-        self.cdll.zs_hmc_ksum_slots.restype = _i64
-        self.cdll.zs_hmc_ksum_slots.argtypes = [_p, ctypes.c_int]
-        self._fn = {}
-        for sfx in ("_f32", "_f64"):
-            for stem, args in (("zs_hmc_move", _MOVE_ARGS), ("zs_hmc_decide", _DECIDE_ARGS), ("zs_hmc_select", _SELECT_ARGS)):
-                fn = getattr(self.cdll, stem + sfx)
-                fn.restype = ctypes.c_int
-                fn.argtypes = args
-                self._fn[stem + sfx] = fn
-
-    def ksum_slots(self, rows):
-        arr = (_i64 * max(len(rows), 1))(*rows)
-        return int(self.cdll.zs_hmc_ksum_slots(arr, len(rows)))
-
-    def raw(self, name, *args):
-        """The entry point's own return code (0 = ok)."""
-        return self._fn[name](*args)
-
-    def call(self, name, *args):
-        rc = self._fn[name](*args)
-        if rc != 0:
-            raise RuntimeError("%s failed with code %d: %s" % (name, rc, _ERRORS.get(rc, "HIP error")))
-
+_PROTOTYPES = _binding.both({
+    "zs_hmc_move": [ctypes.c_int, _p, ctypes.c_int, _i64, _i64, _p, _p, _u64, _u64, _p, _p],
+    "zs_hmc_decide": [_p, ctypes.c_int, _i64, _p, _p, _p, _p, _p, _p, ctypes.c_int, _d, _d, _d, _d, _u64, _u64, _p, _p],
+    "zs_hmc_select": [_p, ctypes.c_int, _i64, _i64, _p, _p],
+})
+_PROTOTYPES["zs_hmc_ksum_slots"] = (_i64, [_p, ctypes.c_int])          # rows (host array), n_tensors -> slots per chain, -1
 
 _LIB = None
 
 
+def HmcLibrary(path):
+    """A freshly loaded, uncached ``_binding.Library`` of the zs_hmc_* C ABI from the file at ``path``; ``lib()`` keeps the
+    in-tree one."""
+    return _binding.Library(path, who="zhusuan.mcmc.HMC", make_target="hmc", abi_symbol="zs_hmc_abi_version",
+                            abi_version=ABI_VERSION, prototypes=_PROTOTYPES)
+
+
 def lib(path=None):
     """The HMC library (lazy); ``path`` loads another file instead of the in-tree one and does not replace it."""
-    global _LIB
-    if path is not None:
-        return HmcLibrary(path)
-    if _LIB is None:
-        _LIB = HmcLibrary(LIB_PATH)
-    return _LIB
+    return _binding.lazy_lib(globals(), HmcLibrary, path)
 
 
 def _sfx(dtype):
-    if dtype == torch.float32:
-        return "_f32"
-    if dtype == torch.float64:
-        return "_f64"
-    raise RuntimeError("zhusuan.mcmc.HMC: latents and log joints must be float32 or float64, got %s" % dtype)
+    return _binding.suffix(dtype, "zhusuan.mcmc.HMC: latents and log joints must be float32 or float64, got %s")
 
 
 def pieces(row):
@@ -117,29 +75,9 @@ def ksum_slots(rows):
     return sum(pieces(r) for r in rows)
 
 
-def _mask(x):
-    return int(x) & 0xFFFFFFFFFFFFFFFF
-
-
 def _table(n_chains, columns, ref):
     """The host table of a move / select: ``columns`` maps a field name to a list of tensors (or None entries) like ``ref``."""
-    k = len(ref)
-    table = (HmcTensor * max(k, 1))()
-    every, start = [], 0
-    for i in range(k):
-        e = table[i]
-        for name, col in columns.items():
-            t = col[i] if col is not None else None
-            if t is None:
-                continue
-            if t.dtype != ref[0].dtype or t.numel() != ref[i].numel() or not t.is_contiguous():
-                raise RuntimeError("zhusuan.mcmc.HMC: operands of one latent must be contiguous, of one dtype and one size")
-            every.append(t)
-            setattr(e, name, _hip.ptr(t))
-        e.start = start
-        e.row = ref[i].numel() // n_chains
-        start += ref[i].numel()
-    return table, start, every
+    return _binding.flat_table(HmcTensor, columns, ref, "zhusuan.mcmc.HMC", n_chains)
 
 
 def move(kind, n_chains, state, q, p, grad, q0=None, z=None, p0=None, ksum=None, seed=0, call=0, rng_state=None, library=None):
@@ -151,7 +89,7 @@ def move(kind, n_chains, state, q, p, grad, q0=None, z=None, p0=None, ksum=None,
     table, n, every = _table(n_chains, dict(q0=q0, q=q, p=p, grad=grad, z=z, p0=p0), q)
     _hip.require_device(*(every + [state, ksum, rng_state]))
     (library or lib()).call("zs_hmc_move" + _sfx(q[0].dtype), int(kind), table, len(q), n, int(n_chains), _hip.ptr(state),
-                            _hip.ptr(ksum), _mask(seed), _mask(call), _hip.ptr(rng_state), _hip.stream_for(q[0]))
+                            _hip.ptr(ksum), _binding.u64(seed), _binding.u64(call), _hip.ptr(rng_state), _hip.stream_for(q[0]))
 
 
 def decide(chunks, n_chains, logp0, logp1, u, state, out, accept, adapting, delta, gamma, t0, kappa, seed=0, call=0,
@@ -166,7 +104,7 @@ def decide(chunks, n_chains, logp0, logp1, u, state, out, accept, adapting, delt
     _hip.require_device(*every)
     (library or lib()).call("zs_hmc_decide" + _sfx(logp0.dtype), table, len(chunks), int(n_chains), _hip.ptr(logp0), _hip.ptr(logp1),
                             _hip.ptr(u), _hip.ptr(state), _hip.ptr(out), _hip.ptr(accept), int(bool(adapting)), float(delta),
-                            float(gamma), float(t0), float(kappa), _mask(seed), _mask(call), _hip.ptr(rng_state),
+                            float(gamma), float(t0), float(kappa), _binding.u64(seed), _binding.u64(call), _hip.ptr(rng_state),
                             _hip.stream_for(logp0))
 
 

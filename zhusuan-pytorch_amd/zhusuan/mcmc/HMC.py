@@ -11,6 +11,7 @@ import collections
 import torch
 
 from .. import _hmc_hip, _rng
+from ._chunks import Chunk, plan_chunks
 
 __all__ = [
     "HMC", "HMCInfo"
@@ -24,23 +25,12 @@ HMCInfo = collections.namedtuple("HMCInfo", ["samples", "acceptance_rate", "upda
 _CHUNK_CALL_STRIDE = 1 << 40
 
 
-class _Chunk(object):
+class _Chunk(Chunk):
     """The latents of one launch: at most _hmc_hip.MAX_TENSORS tensors of one dtype, forming one flat index space."""
 
     def __init__(self, idx, shapes, dtype, n_chains):
-        self.idx = idx
-        self.shapes = shapes
-        self.dtype = dtype
-        self.sizes = [int(torch.Size(s).numel()) for s in shapes]
-        self.n = sum(self.sizes)
+        super().__init__(idx, shapes, dtype)
         self.slots = _hmc_hip.ksum_slots([k // n_chains for k in self.sizes])
-
-    def split(self, flat):
-        out, a = [], 0
-        for s, k in zip(self.shapes, self.sizes):
-            out.append(flat[a:a + k].view(s))
-            a += k
-        return out
 
 
 class HMC(object):
@@ -101,15 +91,8 @@ class HMC(object):
         key = (tuple(names), tuple(tuple(q.shape) for q in qs), tuple(q.dtype for q in qs), n_chains)
         if key == self._plan_key:
             return self._chunks
-        groups = {}
-        for i, q in enumerate(qs):
-            if q.numel():
-                groups.setdefault(q.dtype, []).append(i)
-        chunks = []
-        for dtype, idx in groups.items():
-            for a in range(0, len(idx), _hmc_hip.MAX_TENSORS):
-                part = idx[a:a + _hmc_hip.MAX_TENSORS]
-                chunks.append(_Chunk(part, [qs[i].shape for i in part], dtype, n_chains))
+        chunks = [_Chunk(part, [qs[i].shape for i in part], dtype, n_chains)
+                  for dtype, part in plan_chunks(qs, lambda q: q.dtype, _hmc_hip.MAX_TENSORS)]
         if len(chunks) > _hmc_hip.MAX_CHUNKS:
             raise RuntimeError("zhusuan.mcmc.HMC: more than %d latents" % (_hmc_hip.MAX_CHUNKS * _hmc_hip.MAX_TENSORS))
         self._plan_key, self._chunks = key, chunks

@@ -4,30 +4,20 @@ import torch
 import torch.nn as nn
 
 from .. import _mcmc_hip, _rng
+from ._chunks import Chunk, plan_chunks
 
 __all__ = [
     "SGMCMC"
 ]
 
 
-class _Chunk(object):
+class _Chunk(Chunk):
     """The latents of one launch: at most _mcmc_hip.MAX_TENSORS tensors of one dtype, forming one flat index space."""
 
     def __init__(self, idx, shapes, dtype, device):
-        self.idx = idx
-        self.shapes = shapes
-        self.dtype = dtype
+        super().__init__(idx, shapes, dtype)
         self.device = device
-        self.sizes = [int(torch.Size(s).numel()) for s in shapes]
-        self.n = sum(self.sizes)
         self.state = None          # flat, device-resident (PSGLD's second moment, SGHMC's velocity)
-
-    def split(self, flat):
-        out, a = [], 0
-        for s, k in zip(self.shapes, self.sizes):
-            out.append(flat[a:a + k].view(s))
-            a += k
-        return out
 
     def key(self):
         return (tuple(self.idx), tuple(tuple(s) for s in self.shapes), self.dtype, self.device)
@@ -65,17 +55,11 @@ class SGMCMC(nn.Module):
     def _plan(self):
         """Group the latents into launches; the state of a group survives a resample that keeps its layout (the reference
         keeps ``aux`` / ``vs`` across ``resample=True``, SGLD.py:68-69, SGHMC.py:26-27)."""
-        groups = {}
-        for i, q in enumerate(self._var_list):
-            if q.numel():
-                groups.setdefault((q.dtype, q.device), []).append(i)
         old = dict((c.key(), c) for c in self._chunks)
         chunks = []
-        for (dtype, device), idx in groups.items():
-            for a in range(0, len(idx), _mcmc_hip.MAX_TENSORS):
-                part = idx[a:a + _mcmc_hip.MAX_TENSORS]
-                c = _Chunk(part, [self._var_list[i].shape for i in part], dtype, device)
-                chunks.append(old.get(c.key(), c))
+        for (dtype, device), part in plan_chunks(self._var_list, lambda q: (q.dtype, q.device), _mcmc_hip.MAX_TENSORS):
+            c = _Chunk(part, [self._var_list[i].shape for i in part], dtype, device)
+            chunks.append(old.get(c.key(), c))
         self._chunks = chunks
 
     def _draws(self, chunk):
