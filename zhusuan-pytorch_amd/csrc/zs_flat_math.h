@@ -1,4 +1,4 @@
-// What the satellite libraries (zs_mcmc.hip, zs_hmc.hip, zs_flow.hip) share: the explicit fma, the index maps of a flat index
+// What the satellite libraries (zs_mcmc.hip, zs_hmc.hip, zs_flow.hip, zs_cat.hip) share: the explicit fma, the index maps of a flat index
 // space over a table of tensors, and the 16-byte group of four.  __host__ __device__, so that the host-side sanitizer tests
 // (tests/host_math/) run the same code.
 #pragma once

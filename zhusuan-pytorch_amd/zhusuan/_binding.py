@@ -1,6 +1,6 @@
 """What every ctypes binding of this package shares: the loaded-library class, the lazy ``lib(path=None)`` contract of the
 satellite libraries, the float32 / float64 suffix, the 64-bit mask of a Philox (seed, call) and the pointer table of a flat
-index space.  ``_hip.py`` (main library), ``_mcmc_hip.py``, ``_flow_hip.py`` and ``_hmc_hip.py`` hold only what is their own:
+index space.  ``_hip.py`` (main library), ``_mcmc_hip.py``, ``_flow_hip.py``, ``_hmc_hip.py`` and ``_cat_hip.py`` hold only what is their own:
 constants, ``ctypes.Structure``s, a prototype table and their marshalling functions."""
 import ctypes
 import os

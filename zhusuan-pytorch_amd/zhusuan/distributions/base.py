@@ -17,6 +17,8 @@ class Distribution(object):
     # objectives may then hand the draw to the generator detached.  Uniform is NOT one of them: its draw is rescaled
     # outside the no-grad region (uniform.py:63-70) and carries d/d low = 1 - u, d/d high = u.
     _nonreparam_draw_has_zero_grad = False
+    # trailing axes of a VALUE that belong to one event and not to the batch shape (1 for the one-hot / simplex families)
+    _event_ndims = 0
 
     def __init__(self,
                  dtype,

@@ -5,7 +5,7 @@ import torch.nn as nn
 
 from .stochastic_tensor import StochasticTensor, node_value
 from ..distributions import (Distribution, Normal, Bernoulli, Logistic, Uniform, Beta, Exponential, Gamma, Laplace, Poisson,
-                             StudentT)
+                             StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete)
 
 __all__ = ['BayesianNet']
 
@@ -22,6 +22,11 @@ name_mapping = {
     "Poisson": Poisson,
     "StudentT": StudentT,
     "Uniform": Uniform,
+    # the categorical kernels (include/zs_cat.h)
+    "Categorical": Categorical,
+    "OnehotCategorical": OnehotCategorical,
+    "ExpConcrete": ExpConcrete,
+    "Concrete": Concrete,
 }
 
 
@@ -189,3 +194,22 @@ class BayesianNet(nn.Module):
     def studentT(self, name, df, loc=0., scale=1., dtype=None, is_continuous=True, group_ndims=0, n_samples=None, **kwargs):
         return self._family_node(StudentT, name, n_samples, dict(df=df, loc=loc, scale=scale, dtype=dtype,
                                                                  is_continuous=is_continuous, group_ndims=group_ndims), kwargs)
+
+    # the categorical families (include/zs_cat.h; upstream ZhuSuan's bn.py has the same four factories)
+    def categorical(self, name, logits, dtype=None, group_ndims=0, n_samples=None, **kwargs):
+        return self._family_node(Categorical, name, n_samples, dict(logits=logits, dtype=dtype, group_ndims=group_ndims), kwargs)
+
+    def onehot_categorical(self, name, logits, dtype=None, group_ndims=0, n_samples=None, **kwargs):
+        return self._family_node(OnehotCategorical, name, n_samples, dict(logits=logits, dtype=dtype, group_ndims=group_ndims),
+                                 kwargs)
+
+    def exp_concrete(self, name, temperature, logits, dtype=None, is_reparameterized=True, group_ndims=0, n_samples=None,
+                     **kwargs):
+        return self._family_node(ExpConcrete, name, n_samples, dict(temperature=temperature, logits=logits, dtype=dtype,
+                                                                    is_reparameterized=is_reparameterized,
+                                                                    group_ndims=group_ndims), kwargs)
+
+    def concrete(self, name, temperature, logits, dtype=None, is_reparameterized=True, group_ndims=0, n_samples=None, **kwargs):
+        return self._family_node(Concrete, name, n_samples, dict(temperature=temperature, logits=logits, dtype=dtype,
+                                                                 is_reparameterized=is_reparameterized,
+                                                                 group_ndims=group_ndims), kwargs)

@@ -247,7 +247,12 @@ class StochasticTensor(object):
         return plan
 
     def _reduction_plan_of(self, x, dist, g):
-        full = tuple(broadcast_shapes(tuple(torch.as_tensor(x).shape), tuple(dist.batch_shape)))
+        ev = getattr(dist, '_event_ndims', 0)
+        if ev:          # a value with trailing event axes: only its leading axes broadcast against the batch shape
+            vshape = tuple(torch.as_tensor(x).shape)
+            full = tuple(broadcast_shapes(vshape[:len(vshape) - ev], tuple(dist.batch_shape)))
+        else:
+            full = tuple(broadcast_shapes(tuple(torch.as_tensor(x).shape), tuple(dist.batch_shape)))
         nd = len(full) - g  # ndim of dist.log_prob(x)
         mean_dims = _norm_dims(self._reduce_mean_dims, nd)
         sum_dims = _norm_dims(self._reduce_sum_dims, nd)
