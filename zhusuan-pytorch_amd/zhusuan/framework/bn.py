@@ -5,7 +5,7 @@ import torch.nn as nn
 
 from .stochastic_tensor import StochasticTensor, node_value
 from ..distributions import (Distribution, Normal, Bernoulli, Logistic, Uniform, Beta, Exponential, Gamma, Laplace, Poisson,
-                             StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete)
+                             StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete, MultivariateNormalCholesky)
 
 __all__ = ['BayesianNet']
 
@@ -27,6 +27,8 @@ name_mapping = {
     "OnehotCategorical": OnehotCategorical,
     "ExpConcrete": ExpConcrete,
     "Concrete": Concrete,
+    # the triangular kernels (include/zs_mvn.h)
+    "MultivariateNormalCholesky": MultivariateNormalCholesky,
 }
 
 
@@ -213,3 +215,10 @@ class BayesianNet(nn.Module):
         return self._family_node(Concrete, name, n_samples, dict(temperature=temperature, logits=logits, dtype=dtype,
                                                                  is_reparameterized=is_reparameterized,
                                                                  group_ndims=group_ndims), kwargs)
+
+    # include/zs_mvn.h; upstream ZhuSuan's bn.py has the same factory
+    def multivariate_normal_cholesky(self, name, mean, cov_tril, dtype=None, is_reparameterized=True, group_ndims=0,
+                                     n_samples=None, **kwargs):
+        return self._family_node(MultivariateNormalCholesky, name, n_samples,
+                                 dict(mean=mean, cov_tril=cov_tril, dtype=dtype, is_reparameterized=is_reparameterized,
+                                      group_ndims=group_ndims), kwargs)
