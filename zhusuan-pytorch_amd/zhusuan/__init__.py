@@ -19,3 +19,9 @@ from .graph import GraphedStep, GraphedStages
 from .framework.stochastic_tensor import skip_discarded_draws
 from .layers import particle_linear, particle_mlp, particle_rmse, Linear, Sequential
 from . import optim
+
+
+def is_loglikelihood(generator, variational, observed, axis=0):
+    """``zhusuan.evaluation.is_loglikelihood`` (the package is imported on first use, like ``zhusuan.variational``)."""
+    from .evaluation import is_loglikelihood as _is_loglikelihood
+    return _is_loglikelihood(generator, variational, observed, axis=axis)
