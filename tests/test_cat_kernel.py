@@ -240,48 +240,57 @@ def logmass_tol(dtype, N, logits, idx=None, w=None):
     return eps_sum(dtype, N) * (1 + s)
 
 
+def check_draw_and_log_mass(lib, N, R, K, scale, dtypes=(F32, F64), shifts=(0, 1), d=None):
+    """C1 and C2 on one shape (inputs `d`, by default case_inputs(N, R, K, scale)); returns {dtype: (idx, onehot, lp, lp at the
+    index, lp of the weights, lp of the one-hot)} (CPU) of the first layout in `shifts`."""
+    d = case_inputs(N, R, K, scale) if d is None else d
+    lg, u, w = d["logits"], d["u"], d["w"]
+    skip, tidx, tlp = undecided(lg, u)
+    assert float(skip.double().mean()) <= 0.02, (N, R, K, scale, float(skip.double().mean()))
+    tw = cat_host.reference_logprob_weights(lg, w)
+    found = {}
+    for dtype in dtypes:
+        res = []
+        for shift in shifts:
+            ar = Arena(shift)
+            dl, du, dw = ar.put(lg, dtype), ar.put(u, dtype), ar.put(w, dtype)
+            rc, idx, oh, lp = c1(lib, dtype, ar, dl, du, K, R, N)
+            assert rc == 0
+            rc, idx_b, oh_b, lp_b = c1(lib, dtype, ar, dl, du, K, R, N)          # the same call again
+            rc2, lp2 = c2(lib, dtype, ar, dl, idx, None, K, R, N)
+            rc3, lpw = c2(lib, dtype, ar, dl, None, dw, K, R, N)
+            rc4, lpoh = c2(lib, dtype, ar, dl, None, oh, K, R, N)
+            assert rc == 0 and rc2 == 0 and rc3 == 0 and rc4 == 0
+            torch.cuda.synchronize()
+            ar.check_guards()
+            assert same_bits(idx, idx_b) and same_bits(oh, oh_b) and same_bits(lp, lp_b)
+            res.append((idx.cpu(), oh.cpu(), lp.cpu(), lp2.cpu(), lpw.cpu(), lpoh.cpu()))
+        for a, b in zip(res[0], res[-1]):
+            assert same_bits(a, b), "the aligned and the shifted layout differ (N=%d R=%d K=%d)" % (N, R, K)
+        found[dtype] = res[0]
+        idx, oh, lp, lp2, lpw, lpoh = res[0]
+        idx = idx.view(K, R)
+        assert bool(((idx >= 0) & (idx < N)).all())
+        assert torch.equal(idx[~skip], tidx[~skip]), "a draw outside the margin differs from the float64 argmax"
+        assert torch.equal(oh.view(K, R, N), torch.nn.functional.one_hot(idx, N).to(dtype)), "onehot is not the indicator"
+        assert same_bits(lp, lp2), "C1's lp is not C2's at the drawn index"
+        if N > 1:
+            assert not bool((lg[torch.arange(R)[None].expand(K, R), idx] == -math.inf).any()), "a -inf category was drawn"
+        else:
+            assert bool((idx == 0).all()) and bool((lp == 0).all())
+        own = cat_host.reference_logprob_index(lg, idx)
+        assert_close("C1 lp", lp.view(K, R), own, logmass_tol(dtype, N, lg, idx=idx))
+        assert_close("C2 weights", lpw.view(K, R), tw, logmass_tol(dtype, N, lg, w=w))
+        # the one-hot value through the weights form: the same number as the index form, to the same bound
+        assert_close("C2 one-hot", lpoh.view(K, R), own, logmass_tol(dtype, N, lg, idx=idx))
+    return found
+
+
 @pytest.mark.parametrize("N", NS)
 def test_draw_and_log_mass(lib, N):
     for R, K in grid(N):
         for scale in SCALES:
-            d = case_inputs(N, R, K, scale)
-            lg, u, w = d["logits"], d["u"], d["w"]
-            skip, tidx, tlp = undecided(lg, u)
-            assert float(skip.double().mean()) <= 0.02, (N, R, K, scale, float(skip.double().mean()))
-            tw = cat_host.reference_logprob_weights(lg, w)
-            for dtype in (F32, F64):
-                res = []
-                for shift in (0, 1):
-                    ar = Arena(shift)
-                    dl, du, dw = ar.put(lg, dtype), ar.put(u, dtype), ar.put(w, dtype)
-                    rc, idx, oh, lp = c1(lib, dtype, ar, dl, du, K, R, N)
-                    assert rc == 0
-                    rc, idx_b, oh_b, lp_b = c1(lib, dtype, ar, dl, du, K, R, N)          # the same call again
-                    rc2, lp2 = c2(lib, dtype, ar, dl, idx, None, K, R, N)
-                    rc3, lpw = c2(lib, dtype, ar, dl, None, dw, K, R, N)
-                    rc4, lpoh = c2(lib, dtype, ar, dl, None, oh, K, R, N)
-                    assert rc == 0 and rc2 == 0 and rc3 == 0 and rc4 == 0
-                    torch.cuda.synchronize()
-                    ar.check_guards()
-                    assert same_bits(idx, idx_b) and same_bits(oh, oh_b) and same_bits(lp, lp_b)
-                    res.append((idx.cpu(), oh.cpu(), lp.cpu(), lp2.cpu(), lpw.cpu(), lpoh.cpu()))
-                for a, b in zip(*res):
-                    assert same_bits(a, b), "the aligned and the shifted layout differ (N=%d R=%d K=%d)" % (N, R, K)
-                idx, oh, lp, lp2, lpw, lpoh = res[0]
-                idx = idx.view(K, R)
-                assert bool(((idx >= 0) & (idx < N)).all())
-                assert torch.equal(idx[~skip], tidx[~skip]), "a draw outside the margin differs from the float64 argmax"
-                assert torch.equal(oh.view(K, R, N), torch.nn.functional.one_hot(idx, N).to(dtype)), "onehot is not the indicator"
-                assert same_bits(lp, lp2), "C1's lp is not C2's at the drawn index"
-                if N > 1:
-                    assert not bool((lg[torch.arange(R)[None].expand(K, R), idx] == -math.inf).any()), "a -inf category was drawn"
-                else:
-                    assert bool((idx == 0).all()) and bool((lp == 0).all())
-                own = cat_host.reference_logprob_index(lg, idx)
-                assert_close("C1 lp", lp.view(K, R), own, logmass_tol(dtype, N, lg, idx=idx))
-                assert_close("C2 weights", lpw.view(K, R), tw, logmass_tol(dtype, N, lg, w=w))
-                # the one-hot value through the weights form: the same number as the index form, to the same bound
-                assert_close("C2 one-hot", lpoh.view(K, R), own, logmass_tol(dtype, N, lg, idx=idx))
+            check_draw_and_log_mass(lib, N, R, K, scale)
 
 
 def test_value_without_the_particle_axis_is_shared(lib):
@@ -356,51 +365,59 @@ def relaxed_tols(dtype, N, lg, u, tau, y, exp_space):
     return ytol, eps_sum(dtype, N) * (1 + s)
 
 
+def check_relaxed_draw_and_density(lib, N, R, K, scale, tau, exp_space, dtypes=(F32, F64), shifts=(0, 1), d=None):
+    """C3 and C4 on one shape; returns {dtype: (y, exp(y) or None, lp, C4's lp at that y)} (CPU) of the first layout in `shifts`."""
+    d = case_inputs(N, R, K, scale) if d is None else d
+    lg, u = d["logits"], d["u"]
+    ty, tlp = cat_host.reference_relaxed(lg, u, tau, exp_space)
+    found = {}
+    for dtype in dtypes:
+        res = []
+        for shift in shifts:
+            ar = Arena(shift)
+            dl, du = ar.put(lg, dtype), ar.put(u, dtype)
+            rc, y, ey, lp = c3(lib, dtype, ar, dl, du, tau, exp_space, K, R, N)
+            rc1, y_b, ey_b, lp_b = c3(lib, dtype, ar, dl, du, tau, exp_space, K, R, N)
+            rc2, lp4 = c4(lib, dtype, ar, dl, y, tau, exp_space, K, R, N)
+            assert rc == 0 and rc1 == 0 and rc2 == 0
+            torch.cuda.synchronize()
+            ar.check_guards()
+            assert same_bits(y, y_b) and same_bits(ey, ey_b) and same_bits(lp, lp_b)
+            res.append((y.cpu(), None if ey is None else ey.cpu(), lp.cpu(), lp4.cpu()))
+        for a, b in zip(res[0], res[-1]):
+            assert same_bits(a, b), "the aligned and the shifted layout differ (N=%d R=%d K=%d)" % (N, R, K)
+        found[dtype] = res[0]
+        y, ey, lp, lp4 = res[0]
+        y = y.view(K, R, N)
+        ytol, lptol = relaxed_tols(dtype, N, lg, u, tau, ty, exp_space)
+        assert_close("C3 y", y, ty, ytol[..., None].expand_as(ty))
+        lse_y = torch.logsumexp(y.to(F64), dim=-1)
+        ok = torch.isfinite(lse_y)
+        assert bool((lse_y[ok].abs() <= ytol[ok]).all()), "y is not normalised"
+        assert_close("C3 lp %s" % ((N, R, K, scale, tau, exp_space),), lp.view(K, R), tlp, lptol)
+        # C4 at the device's own y: the truth at that y, to the bound at that y
+        t4 = cat_host.reference_relaxed_logprob(lg, y, tau, exp_space)
+        _, lptol4 = relaxed_tols(dtype, N, lg, u, tau, y.to(F64), exp_space)
+        assert_close("C4 lp", lp4.view(K, R), t4, lptol4)
+        if exp_space:
+            # exp(y) is the exp of the stored y by the kernels' own device function (zs_cat_exp runs it element-wise)
+            ar = Arena(0)
+            dy = ar.put(y)
+            out = ar.out(y.numel(), dtype)
+            assert lib.raw("zs_cat_exp" + sfx(dtype), _ptr(dy), _ptr(out), y.numel(), _stream()) == 0
+            torch.cuda.synchronize()
+            ar.check_guards()
+            assert same_bits(out, ey), "exp(y) is not the device exp of the y written"
+    return found
+
+
 @pytest.mark.parametrize("N", NS)
 def test_relaxed_draw_and_density(lib, N):
     for R, K in grid(N):
         for ci, scale in enumerate(SCALES):
             tau = TAUS[(ci + KS.index(K) + RS.index(R if R in RS else 1)) % 4]
             exp_space = (ci + K) % 2
-            d = case_inputs(N, R, K, scale)
-            lg, u = d["logits"], d["u"]
-            ty, tlp = cat_host.reference_relaxed(lg, u, tau, exp_space)
-            for dtype in (F32, F64):
-                res = []
-                for shift in (0, 1):
-                    ar = Arena(shift)
-                    dl, du = ar.put(lg, dtype), ar.put(u, dtype)
-                    rc, y, ey, lp = c3(lib, dtype, ar, dl, du, tau, exp_space, K, R, N)
-                    rc1, y_b, ey_b, lp_b = c3(lib, dtype, ar, dl, du, tau, exp_space, K, R, N)
-                    rc2, lp4 = c4(lib, dtype, ar, dl, y, tau, exp_space, K, R, N)
-                    assert rc == 0 and rc1 == 0 and rc2 == 0
-                    torch.cuda.synchronize()
-                    ar.check_guards()
-                    assert same_bits(y, y_b) and same_bits(ey, ey_b) and same_bits(lp, lp_b)
-                    res.append((y.cpu(), None if ey is None else ey.cpu(), lp.cpu(), lp4.cpu()))
-                for a, b in zip(*res):
-                    assert same_bits(a, b), "the aligned and the shifted layout differ (N=%d R=%d K=%d)" % (N, R, K)
-                y, ey, lp, lp4 = res[0]
-                y = y.view(K, R, N)
-                ytol, lptol = relaxed_tols(dtype, N, lg, u, tau, ty, exp_space)
-                assert_close("C3 y", y, ty, ytol[..., None].expand_as(ty))
-                lse_y = torch.logsumexp(y.to(F64), dim=-1)
-                ok = torch.isfinite(lse_y)
-                assert bool((lse_y[ok].abs() <= ytol[ok]).all()), "y is not normalised"
-                assert_close("C3 lp %s" % ((N, R, K, scale, tau, exp_space),), lp.view(K, R), tlp, lptol)
-                # C4 at the device's own y: the truth at that y, to the bound at that y
-                t4 = cat_host.reference_relaxed_logprob(lg, y, tau, exp_space)
-                _, lptol4 = relaxed_tols(dtype, N, lg, u, tau, y.to(F64), exp_space)
-                assert_close("C4 lp", lp4.view(K, R), t4, lptol4)
-                if exp_space:
-                    # exp(y) is the exp of the stored y by the kernels' own device function (zs_cat_exp runs it element-wise)
-                    ar = Arena(0)
-                    dy = ar.put(y)
-                    out = ar.out(y.numel(), dtype)
-                    assert lib.raw("zs_cat_exp" + sfx(dtype), _ptr(dy), _ptr(out), y.numel(), _stream()) == 0
-                    torch.cuda.synchronize()
-                    ar.check_guards()
-                    assert same_bits(out, ey), "exp(y) is not the device exp of the y written"
+            check_relaxed_draw_and_density(lib, N, R, K, scale, tau, exp_space)
 
 
 # ------------------------------------------------------------------------------------------------ backward
@@ -417,52 +434,125 @@ def exponent_eps(dtype):
     return 2.0 * (2.0 ** -24 if dtype == F32 else 2.0 ** -53)
 
 
+def check_log_mass_backward(lib, N, R, K, scale, dtypes=(F32, F64), shifts=(0, 1), d=None):
+    """C2's backward on one shape (inputs without a -inf logit); returns {dtype: (glogits of the index form, glogits and gx of the
+    weights form)} (CPU) of the first layout in `shifts`."""
+    d = case_inputs(N, R, K, scale, neg_inf=False) if d is None else d
+    lg, w, g, u = d["logits"], d["w"], d["g"], d["u"]
+    idx = cat_host.reference_sample(lg, u)[0]
+    sm = torch.softmax(lg, dim=1)
+    lse = torch.logsumexp(lg, dim=1)
+    truths = {}
+    for form, x in (("index", torch.nn.functional.one_hot(idx, N).to(F64)), ("weights", w)):
+        l0 = lg.clone().requires_grad_(True)
+        x0 = x.clone().requires_grad_(True)
+        lp = (x0 * l0[None]).sum(-1) - x0.sum(-1) * torch.logsumexp(l0, dim=1)[None]
+        gl, gx = torch.autograd.grad(lp, [l0, x0], g)
+        # terms of glogits: |g x| and |g sx softmax| over k; the softmax is exp(l - lse)
+        soft = ((g.abs() * x.sum(-1).abs()).sum(0))[:, None] * sm
+        s_gl = (g.abs()[..., None] * x.abs()).sum(0) + soft
+        x_gl = soft * (lg.abs() + lse.abs()[:, None])
+        s_gx = g.abs()[..., None] * (lg.abs() + lse.abs()[:, None])[None]
+        truths[form] = (x, gl, gx, s_gl, x_gl, s_gx)
+    found = {}
+    for dtype in dtypes:
+        res = []
+        for shift in shifts:
+            ar = Arena(shift)
+            dl, dg = ar.put(lg, dtype), ar.put(g, dtype)
+            didx = ar.put(idx)
+            rc, gl_i, _ = c2b(lib, dtype, ar, dl, didx, None, dg, K, R, N, False)
+            rc1, gl_i2, _ = c2b(lib, dtype, ar, dl, didx, None, dg, K, R, N, False)
+            dw = ar.put(w, dtype)
+            rc2, gl_w, gx_w = c2b(lib, dtype, ar, dl, None, dw, dg, K, R, N, True)
+            rc3, gl_w2, gx_w2 = c2b(lib, dtype, ar, dl, None, dw, dg, K, R, N, True)
+            assert rc == 0 and rc1 == 0 and rc2 == 0 and rc3 == 0
+            torch.cuda.synchronize()
+            ar.check_guards()
+            assert same_bits(gl_i, gl_i2) and same_bits(gl_w, gl_w2) and same_bits(gx_w, gx_w2), \
+                "K-summed gradients differ between two calls"
+            res.append((gl_i.cpu(), gl_w.cpu(), gx_w.cpu()))
+        for a, b in zip(res[0], res[-1]):
+            assert same_bits(a, b), "the aligned and the shifted layout differ (N=%d R=%d K=%d)" % (N, R, K)
+        found[dtype] = res[0]
+        gl_i, gl_w, gx_w = res[0]
+        e, ee = bwd_tol(dtype, N, K), exponent_eps(dtype)
+        for form, got in (("index", gl_i), ("weights", gl_w)):
+            x, gl, gx, s_gl, x_gl, s_gx = truths[form]
+            assert_close("glogits (%s)" % form, got.view(R, N), gl, e * s_gl + ee * x_gl + 1e-300)
+        assert_close("gx", gx_w.view(K, R, N), truths["weights"][2], e * truths["weights"][5] + 1e-300)
+    return found
+
+
 @pytest.mark.parametrize("N", NS)
 def test_log_mass_backward(lib, N):
     for R, K in grid(N):
         for scale in SCALES:
-            d = case_inputs(N, R, K, scale, neg_inf=False)
-            lg, w, g, u = d["logits"], d["w"], d["g"], d["u"]
-            idx = cat_host.reference_sample(lg, u)[0]
-            sm = torch.softmax(lg, dim=1)
-            lse = torch.logsumexp(lg, dim=1)
-            truths = {}
-            for form, x in (("index", torch.nn.functional.one_hot(idx, N).to(F64)), ("weights", w)):
-                l0 = lg.clone().requires_grad_(True)
-                x0 = x.clone().requires_grad_(True)
-                lp = (x0 * l0[None]).sum(-1) - x0.sum(-1) * torch.logsumexp(l0, dim=1)[None]
-                gl, gx = torch.autograd.grad(lp, [l0, x0], g)
-                # terms of glogits: |g x| and |g sx softmax| over k; the softmax is exp(l - lse)
-                soft = ((g.abs() * x.sum(-1).abs()).sum(0))[:, None] * sm
-                s_gl = (g.abs()[..., None] * x.abs()).sum(0) + soft
-                x_gl = soft * (lg.abs() + lse.abs()[:, None])
-                s_gx = g.abs()[..., None] * (lg.abs() + lse.abs()[:, None])[None]
-                truths[form] = (x, gl, gx, s_gl, x_gl, s_gx)
-            for dtype in (F32, F64):
-                res = []
-                for shift in (0, 1):
-                    ar = Arena(shift)
-                    dl, dg = ar.put(lg, dtype), ar.put(g, dtype)
-                    didx = ar.put(idx)
-                    rc, gl_i, _ = c2b(lib, dtype, ar, dl, didx, None, dg, K, R, N, False)
-                    rc1, gl_i2, _ = c2b(lib, dtype, ar, dl, didx, None, dg, K, R, N, False)
-                    dw = ar.put(w, dtype)
-                    rc2, gl_w, gx_w = c2b(lib, dtype, ar, dl, None, dw, dg, K, R, N, True)
-                    rc3, gl_w2, gx_w2 = c2b(lib, dtype, ar, dl, None, dw, dg, K, R, N, True)
-                    assert rc == 0 and rc1 == 0 and rc2 == 0 and rc3 == 0
-                    torch.cuda.synchronize()
-                    ar.check_guards()
-                    assert same_bits(gl_i, gl_i2) and same_bits(gl_w, gl_w2) and same_bits(gx_w, gx_w2), \
-                        "K-summed gradients differ between two calls"
-                    res.append((gl_i.cpu(), gl_w.cpu(), gx_w.cpu()))
-                for a, b in zip(*res):
-                    assert same_bits(a, b), "the aligned and the shifted layout differ (N=%d R=%d K=%d)" % (N, R, K)
-                gl_i, gl_w, gx_w = res[0]
-                e, ee = bwd_tol(dtype, N, K), exponent_eps(dtype)
-                for form, got in (("index", gl_i), ("weights", gl_w)):
-                    x, gl, gx, s_gl, x_gl, s_gx = truths[form]
-                    assert_close("glogits (%s)" % form, got.view(R, N), gl, e * s_gl + ee * x_gl + 1e-300)
-                assert_close("gx", gx_w.view(K, R, N), truths["weights"][2], e * truths["weights"][5] + 1e-300)
+            check_log_mass_backward(lib, N, R, K, scale)
+
+
+def check_relaxed_backward(lib, N, R, K, scale, tau, exp_space, dtypes=(F32, F64), shifts=(0, 1), d=None):
+    """The backwards of C3 and C4 on one shape (inputs without a -inf logit); returns {dtype: (y, C3's glogits, C4's gy, C4's
+    glogits)} (CPU) of the first layout in `shifts`."""
+    d = case_inputs(N, R, K, scale, neg_inf=False) if d is None else d
+    lg, u, g, gy, gey = d["logits"], d["u"], d["g"], d["gy"], d["gey"]
+    found = {}
+    for dtype in dtypes:
+        res = []
+        for shift in shifts:
+            ar = Arena(shift)
+            dl, du = ar.put(lg, dtype), ar.put(u, dtype)
+            rc, y, ey, lp = c3(lib, dtype, ar, dl, du, tau, exp_space, K, R, N)
+            dgy, dgey, dg = ar.put(gy, dtype), (ar.put(gey, dtype) if exp_space else None), ar.put(g, dtype)
+            rc1, gl3 = c3b(lib, dtype, ar, dl, y, tau, exp_space, dgy, dgey, dg, K, R, N)
+            rc2, gl3_b = c3b(lib, dtype, ar, dl, y, tau, exp_space, dgy, dgey, dg, K, R, N)
+            rc3, gy4, gl4 = c4b(lib, dtype, ar, dl, y, tau, exp_space, dg, K, R, N)
+            rc4, gy4_b, gl4_b = c4b(lib, dtype, ar, dl, y, tau, exp_space, dg, K, R, N)
+            assert rc == 0 and rc1 == 0 and rc2 == 0 and rc3 == 0 and rc4 == 0
+            torch.cuda.synchronize()
+            ar.check_guards()
+            assert same_bits(gl3, gl3_b) and same_bits(gl4, gl4_b) and same_bits(gy4, gy4_b), \
+                "K-summed gradients differ between two calls"
+            res.append((y.cpu(), gl3.cpu(), gy4.cpu(), gl4.cpu()))
+        for a, b in zip(res[0], res[-1]):
+            assert same_bits(a, b), "the aligned and the shifted layout differ (N=%d R=%d K=%d)" % (N, R, K)
+        found[dtype] = res[0]
+        ys, gl3, gy4, gl4 = res[0]
+        ys = ys.view(K, R, N).to(F64)
+        # float64 autograd of the restatement at the noise that reproduces the saved y: gumbel = tau y_saved - logits
+        gum = tau * ys - lg[None]
+        l0 = lg.clone().requires_grad_(True)
+        a = (l0[None] + gum) / tau
+        yv = a - torch.logsumexp(a, dim=-1, keepdim=True)
+        lpv = cat_host.reference_relaxed_logprob(l0, yv, tau, exp_space)
+        out = (gy * yv).sum() + (g * lpv).sum() + ((gey * torch.exp(yv)).sum() if exp_space else 0.0)
+        t3, = torch.autograd.grad(out, [l0])
+        y1 = ys.clone().requires_grad_(True)
+        l1 = lg.clone().requires_grad_(True)
+        t4y, t4l = torch.autograd.grad(cat_host.reference_relaxed_logprob(l1, y1, tau, exp_space), [y1, l1], g)
+        # magnitudes of the terms added (header formulas); q = 1 - N softmax(t) carries the softmax exp(t - lse t)
+        e_ = 1.0 if exp_space else 0.0
+        ga = g.abs()[..., None]
+        t = lg[None] - tau * ys
+        lse_t = torch.logsumexp(t, dim=-1, keepdim=True)
+        nsm = N * torch.softmax(t, dim=-1)
+        qa = 1 + nsm
+        dq = nsm * (t.abs() + lse_t.abs())          # times exponent_eps: the rounding of q
+        ex = torch.exp(ys)
+        G = gy.abs() + (gey.abs() * ex if exp_space else 0.0) + ga * (tau * qa + e_)
+        s3 = ((G + ex * G.sum(-1, keepdim=True)) / tau + ga * qa).sum(0)
+        # q enters G (times tau, over tau) and the direct term; exp(y) stands for softmax(a) = exp(a - lse a), whose
+        # exponent the stored y carries rounded
+        aa = cat_host.reference_perturbed(lg, u) / tau
+        da = ex * (aa.abs() + torch.logsumexp(aa, dim=-1, keepdim=True).abs())
+        x3 = (2 * ga * dq + da * G.sum(-1, keepdim=True) / tau).sum(0)
+        s4y, x4y = ga * (tau * qa + e_), ga * tau * dq
+        s4l, x4l = (ga * qa).sum(0), (ga * dq).sum(0)
+        e, ee = bwd_tol(dtype, N, K), exponent_eps(dtype)
+        assert_close("C3 glogits %s" % ((N, R, K, scale, tau, exp_space),), gl3.view(R, N), t3, e * s3 + ee * x3)
+        assert_close("C4 gy", gy4.view(K, R, N), t4y, e * s4y + ee * x4y)
+        assert_close("C4 glogits", gl4.view(R, N), t4l, e * s4l + ee * x4l)
+    return found
 
 
 @pytest.mark.parametrize("N", NS)
@@ -472,62 +562,7 @@ def test_relaxed_backward(lib, N):
         for si, scale in enumerate(SCALES):
             tau = TAUS[(ci + si) % 4]
             exp_space = (ci + si) % 2
-            d = case_inputs(N, R, K, scale, neg_inf=False)
-            lg, u, g, gy, gey = d["logits"], d["u"], d["g"], d["gy"], d["gey"]
-            for dtype in (F32, F64):
-                res = []
-                for shift in (0, 1):
-                    ar = Arena(shift)
-                    dl, du = ar.put(lg, dtype), ar.put(u, dtype)
-                    rc, y, ey, lp = c3(lib, dtype, ar, dl, du, tau, exp_space, K, R, N)
-                    dgy, dgey, dg = ar.put(gy, dtype), (ar.put(gey, dtype) if exp_space else None), ar.put(g, dtype)
-                    rc1, gl3 = c3b(lib, dtype, ar, dl, y, tau, exp_space, dgy, dgey, dg, K, R, N)
-                    rc2, gl3_b = c3b(lib, dtype, ar, dl, y, tau, exp_space, dgy, dgey, dg, K, R, N)
-                    rc3, gy4, gl4 = c4b(lib, dtype, ar, dl, y, tau, exp_space, dg, K, R, N)
-                    rc4, gy4_b, gl4_b = c4b(lib, dtype, ar, dl, y, tau, exp_space, dg, K, R, N)
-                    assert rc == 0 and rc1 == 0 and rc2 == 0 and rc3 == 0 and rc4 == 0
-                    torch.cuda.synchronize()
-                    ar.check_guards()
-                    assert same_bits(gl3, gl3_b) and same_bits(gl4, gl4_b) and same_bits(gy4, gy4_b), \
-                        "K-summed gradients differ between two calls"
-                    res.append((y.cpu(), gl3.cpu(), gy4.cpu(), gl4.cpu()))
-                for a, b in zip(*res):
-                    assert same_bits(a, b), "the aligned and the shifted layout differ (N=%d R=%d K=%d)" % (N, R, K)
-                ys, gl3, gy4, gl4 = res[0]
-                ys = ys.view(K, R, N).to(F64)
-                # float64 autograd of the restatement at the noise that reproduces the saved y: gumbel = tau y_saved - logits
-                gum = tau * ys - lg[None]
-                l0 = lg.clone().requires_grad_(True)
-                a = (l0[None] + gum) / tau
-                yv = a - torch.logsumexp(a, dim=-1, keepdim=True)
-                lpv = cat_host.reference_relaxed_logprob(l0, yv, tau, exp_space)
-                out = (gy * yv).sum() + (g * lpv).sum() + ((gey * torch.exp(yv)).sum() if exp_space else 0.0)
-                t3, = torch.autograd.grad(out, [l0])
-                y1 = ys.clone().requires_grad_(True)
-                l1 = lg.clone().requires_grad_(True)
-                t4y, t4l = torch.autograd.grad(cat_host.reference_relaxed_logprob(l1, y1, tau, exp_space), [y1, l1], g)
-                # magnitudes of the terms added (header formulas); q = 1 - N softmax(t) carries the softmax exp(t - lse t)
-                e_ = 1.0 if exp_space else 0.0
-                ga = g.abs()[..., None]
-                t = lg[None] - tau * ys
-                lse_t = torch.logsumexp(t, dim=-1, keepdim=True)
-                nsm = N * torch.softmax(t, dim=-1)
-                qa = 1 + nsm
-                dq = nsm * (t.abs() + lse_t.abs())          # times exponent_eps: the rounding of q
-                ex = torch.exp(ys)
-                G = gy.abs() + (gey.abs() * ex if exp_space else 0.0) + ga * (tau * qa + e_)
-                s3 = ((G + ex * G.sum(-1, keepdim=True)) / tau + ga * qa).sum(0)
-                # q enters G (times tau, over tau) and the direct term; exp(y) stands for softmax(a) = exp(a - lse a), whose
-                # exponent the stored y carries rounded
-                aa = cat_host.reference_perturbed(lg, u) / tau
-                da = ex * (aa.abs() + torch.logsumexp(aa, dim=-1, keepdim=True).abs())
-                x3 = (2 * ga * dq + da * G.sum(-1, keepdim=True) / tau).sum(0)
-                s4y, x4y = ga * (tau * qa + e_), ga * tau * dq
-                s4l, x4l = (ga * qa).sum(0), (ga * dq).sum(0)
-                e, ee = bwd_tol(dtype, N, K), exponent_eps(dtype)
-                assert_close("C3 glogits %s" % ((N, R, K, scale, tau, exp_space),), gl3.view(R, N), t3, e * s3 + ee * x3)
-                assert_close("C4 gy", gy4.view(K, R, N), t4y, e * s4y + ee * x4y)
-                assert_close("C4 glogits", gl4.view(R, N), t4l, e * s4l + ee * x4l)
+            check_relaxed_backward(lib, N, R, K, scale, tau, exp_space)
 
 
 # ------------------------------------------------------------------------------------------------ guards and rejections

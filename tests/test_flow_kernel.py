@@ -114,156 +114,176 @@ def mask_for(rng, dtype, D, kind):
 
 
 # ------------------------------------------------------------------------------------------------ coupling, MASK
+def check_mask(lib, dtype, B, D, maskkind, rng):
+    """split, merge and their backwards in MASK mode on one [B, D] problem drawn from `rng`, both signs, both layouts"""
+    x, shift, gy = (rnd(rng, dtype, B, D) for _ in range(3))
+    mask = mask_for(rng, dtype, D, maskkind)
+    X, M, SH, G = ld(x), ld(mask), ld(shift), ld(gy)
+    OM = 1 - M
+    for sign in (1.0, -1.0):
+        def run(off):
+            A = Arena(dtype, off)
+            dx, dm, dsh, dg = A.put(x), A.put(mask), A.put(shift), A.put(gy)
+            o_split, o_sbwd, o_y, o_gx, o_gs = (A.out(B, D) for _ in range(5))
+            st = stream()
+            assert lib.raw("zs_flow_split" + sfx(dtype), MASK, dx.data_ptr(), dm.data_ptr(), o_split.data_ptr(), B, D, 0, st) == 0
+            assert lib.raw("zs_flow_split_bwd" + sfx(dtype), MASK, dg.data_ptr(), dm.data_ptr(), o_sbwd.data_ptr(), B, D, 0, st) == 0
+            assert lib.raw("zs_flow_merge" + sfx(dtype), MASK, dx.data_ptr(), dm.data_ptr(), dsh.data_ptr(), sign,
+                           o_y.data_ptr(), B, D, 0, st) == 0
+            assert lib.raw("zs_flow_merge_bwd" + sfx(dtype), MASK, dg.data_ptr(), dm.data_ptr(), sign, o_gx.data_ptr(),
+                           o_gs.data_ptr(), B, D, 0, st) == 0
+            A.guards_intact()
+            within(o_split, M * X, np.abs(M * X), dtype)
+            within(o_sbwd, M * G, np.abs(M * G), dtype)
+            within(o_y, M * X + (OM * X + sign * SH * OM), np.abs(M * X) + np.abs(OM * X) + np.abs(SH * OM), dtype)
+            within(o_gx, M * G + OM * G, np.abs(M * G) + np.abs(OM * G), dtype)
+            within(o_gs, sign * G * OM, np.abs(G * OM), dtype)
+            return [o_split, o_sbwd, o_y, o_gx, o_gs]
+        both_offsets(run)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("B", BS)
 @pytest.mark.parametrize("maskkind", ["binary", "nonbinary"])
 def test_mask_split_merge_and_backwards(lib, dtype, B, maskkind):
     rng = np.random.RandomState(11 + B)
     for D in DS:
-        x, shift, gy = (rnd(rng, dtype, B, D) for _ in range(3))
-        mask = mask_for(rng, dtype, D, maskkind)
-        X, M, SH, G = ld(x), ld(mask), ld(shift), ld(gy)
-        OM = 1 - M
-        for sign in (1.0, -1.0):
-            def run(off):
-                A = Arena(dtype, off)
-                dx, dm, dsh, dg = A.put(x), A.put(mask), A.put(shift), A.put(gy)
-                o_split, o_sbwd, o_y, o_gx, o_gs = (A.out(B, D) for _ in range(5))
-                st = stream()
-                assert lib.raw("zs_flow_split" + sfx(dtype), MASK, dx.data_ptr(), dm.data_ptr(), o_split.data_ptr(), B, D, 0, st) == 0
-                assert lib.raw("zs_flow_split_bwd" + sfx(dtype), MASK, dg.data_ptr(), dm.data_ptr(), o_sbwd.data_ptr(), B, D, 0, st) == 0
-                assert lib.raw("zs_flow_merge" + sfx(dtype), MASK, dx.data_ptr(), dm.data_ptr(), dsh.data_ptr(), sign,
-                               o_y.data_ptr(), B, D, 0, st) == 0
-                assert lib.raw("zs_flow_merge_bwd" + sfx(dtype), MASK, dg.data_ptr(), dm.data_ptr(), sign, o_gx.data_ptr(),
-                               o_gs.data_ptr(), B, D, 0, st) == 0
-                A.guards_intact()
-                within(o_split, M * X, np.abs(M * X), dtype)
-                within(o_sbwd, M * G, np.abs(M * G), dtype)
-                within(o_y, M * X + (OM * X + sign * SH * OM), np.abs(M * X) + np.abs(OM * X) + np.abs(SH * OM), dtype)
-                within(o_gx, M * G + OM * G, np.abs(M * G) + np.abs(OM * G), dtype)
-                within(o_gs, sign * G * OM, np.abs(G * OM), dtype)
-                return [o_split, o_sbwd, o_y, o_gx, o_gs]
-            both_offsets(run)
+        check_mask(lib, dtype, B, D, maskkind, rng)
 
 
 # ------------------------------------------------------------------------------------------------ coupling, INTERLEAVE
+def check_interleave(lib, dtype, B, D, sel, rng):
+    """split, merge and their backwards in INTERLEAVE mode on one [B, D] problem drawn from `rng`, both signs, both layouts"""
+    on = 1 - sel
+    H = D // 2
+    x, gy = rnd(rng, dtype, B, D), rnd(rng, dtype, B, D)
+    shift, gh = rnd(rng, dtype, B, H), rnd(rng, dtype, B, H)
+    X, G, SH = ld(x), ld(gy), ld(shift)
+    for sign in (1.0, -1.0):
+        def run(off):
+            A = Arena(dtype, off)
+            dx, dg, dsh, dgh = A.put(x), A.put(gy), A.put(shift), A.put(gh)
+            o_split, o_gs = A.out(B, H), A.out(B, H)
+            o_sbwd, o_y, o_gx = A.out(B, D), A.out(B, D), A.out(B, D)
+            st = stream()
+            assert lib.raw("zs_flow_split" + sfx(dtype), INTERLEAVE, dx.data_ptr(), None, o_split.data_ptr(), B, D, sel, st) == 0
+            assert lib.raw("zs_flow_split_bwd" + sfx(dtype), INTERLEAVE, dgh.data_ptr(), None, o_sbwd.data_ptr(), B, D, sel, st) == 0
+            assert lib.raw("zs_flow_merge" + sfx(dtype), INTERLEAVE, dx.data_ptr(), None, dsh.data_ptr(), sign, o_y.data_ptr(),
+                           B, D, sel, st) == 0
+            assert lib.raw("zs_flow_merge_bwd" + sfx(dtype), INTERLEAVE, dg.data_ptr(), None, sign, o_gx.data_ptr(),
+                           o_gs.data_ptr(), B, D, sel, st) == 0
+            A.guards_intact()
+            assert torch.equal(o_split, dx[:, sel::2])                                  # copies are exact
+            assert torch.equal(o_sbwd[:, sel::2], dgh) and bool((o_sbwd[:, on::2] == 0).all())
+            assert torch.equal(o_y[:, sel::2], dx[:, sel::2])
+            within(o_y[:, on::2], X[:, on::2] + sign * SH, np.abs(X[:, on::2]) + np.abs(SH), dtype)
+            assert torch.equal(o_gx, dg)
+            assert torch.equal(o_gs, sign * dg[:, on::2])
+            return [o_split, o_sbwd, o_y, o_gx, o_gs]
+        both_offsets(run)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("B", BS)
 @pytest.mark.parametrize("sel", [0, 1])
 def test_interleave_split_merge_and_backwards(lib, dtype, B, sel):
     rng = np.random.RandomState(23 + B + sel)
-    on = 1 - sel
     for D in DS_PAIRS:
-        H = D // 2
-        x, gy = rnd(rng, dtype, B, D), rnd(rng, dtype, B, D)
-        shift, gh = rnd(rng, dtype, B, H), rnd(rng, dtype, B, H)
-        X, G, SH = ld(x), ld(gy), ld(shift)
-        for sign in (1.0, -1.0):
-            def run(off):
-                A = Arena(dtype, off)
-                dx, dg, dsh, dgh = A.put(x), A.put(gy), A.put(shift), A.put(gh)
-                o_split, o_gs = A.out(B, H), A.out(B, H)
-                o_sbwd, o_y, o_gx = A.out(B, D), A.out(B, D), A.out(B, D)
-                st = stream()
-                assert lib.raw("zs_flow_split" + sfx(dtype), INTERLEAVE, dx.data_ptr(), None, o_split.data_ptr(), B, D, sel, st) == 0
-                assert lib.raw("zs_flow_split_bwd" + sfx(dtype), INTERLEAVE, dgh.data_ptr(), None, o_sbwd.data_ptr(), B, D, sel, st) == 0
-                assert lib.raw("zs_flow_merge" + sfx(dtype), INTERLEAVE, dx.data_ptr(), None, dsh.data_ptr(), sign, o_y.data_ptr(),
-                               B, D, sel, st) == 0
-                assert lib.raw("zs_flow_merge_bwd" + sfx(dtype), INTERLEAVE, dg.data_ptr(), None, sign, o_gx.data_ptr(),
-                               o_gs.data_ptr(), B, D, sel, st) == 0
-                A.guards_intact()
-                assert torch.equal(o_split, dx[:, sel::2])                                  # copies are exact
-                assert torch.equal(o_sbwd[:, sel::2], dgh) and bool((o_sbwd[:, on::2] == 0).all())
-                assert torch.equal(o_y[:, sel::2], dx[:, sel::2])
-                within(o_y[:, on::2], X[:, on::2] + sign * SH, np.abs(X[:, on::2]) + np.abs(SH), dtype)
-                assert torch.equal(o_gx, dg)
-                assert torch.equal(o_gs, sign * dg[:, on::2])
-                return [o_split, o_sbwd, o_y, o_gx, o_gs]
-            both_offsets(run)
+        check_interleave(lib, dtype, B, D, sel, rng)
 
 
 # ------------------------------------------------------------------------------------------------ Scaling
+def check_scale(lib, dtype, B, D, rng):
+    """Scaling forward (out of place and in place) and backward on one [B, D] problem drawn from `rng`, both signs, both layouts"""
+    x, gy, ls, gld = rnd(rng, dtype, B, D), rnd(rng, dtype, B, D), rnd(rng, dtype, D), rnd(rng, dtype, 1)
+    X, G, LS = ld(x), ld(gy), ld(ls)
+    for sign in (1.0, -1.0):
+        F = np.exp(sign * LS)
+        Y = X * F
+
+        def run(off):
+            A = Arena(dtype, off)
+            dx, dg, dls, dgl = A.put(x), A.put(gy), A.put(ls), A.put(gld)
+            o_y, o_ld, o_gx, o_gls, o_gls0 = A.out(B, D), A.out(1), A.out(B, D), A.out(D), A.out(D)
+            inplace = A.put(x)
+            o_ld2, o_gls2 = A.out(1), A.out(D)
+            st = stream()
+            name = "zs_flow_scale_fwd" + sfx(dtype)
+            assert lib.raw(name, dx.data_ptr(), dls.data_ptr(), sign, o_y.data_ptr(), o_ld.data_ptr(), B, D, st) == 0
+            assert lib.raw(name, inplace.data_ptr(), dls.data_ptr(), sign, inplace.data_ptr(), o_ld2.data_ptr(), B, D, st) == 0
+            name = "zs_flow_scale_bwd" + sfx(dtype)
+            args = (dg.data_ptr(), o_y.data_ptr(), dls.data_ptr())
+            assert lib.raw(name, *args, dgl.data_ptr(), sign, o_gx.data_ptr(), o_gls.data_ptr(), B, D, st) == 0
+            assert lib.raw(name, *args, dgl.data_ptr(), sign, o_gx.data_ptr(), o_gls2.data_ptr(), B, D, st) == 0
+            assert lib.raw(name, *args, None, sign, o_gx.data_ptr(), o_gls0.data_ptr(), B, D, st) == 0
+            A.guards_intact()
+            within(o_y, Y, np.abs(Y), dtype)
+            assert torch.equal(inplace, o_y), "in place differs from out of place"
+            within(o_ld, LS.sum(), np.abs(LS).sum(), dtype, n=D)
+            assert torch.equal(o_ld, o_ld2) and torch.equal(o_gls, o_gls2), "a reduction is not reproducible"
+            within(o_gx, G * F, np.abs(G * F), dtype)
+            Yk = got(o_y)                      # the backward reads the SAVED output: the truth uses the same numbers
+            S = np.abs(G * Yk).sum(0)
+            within(o_gls, sign * (G * Yk).sum(0) + ld(gld)[0], S + abs(ld(gld)[0]), dtype, n=B + 1)
+            within(o_gls0, sign * (G * Yk).sum(0), S, dtype, n=B)
+            return [o_y, o_ld, o_gx, o_gls, o_gls0]
+        both_offsets(run)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("B", BS)
 def test_scale_forward_and_backward(lib, dtype, B):
     rng = np.random.RandomState(37 + B)
     for D in DS:
-        x, gy, ls, gld = rnd(rng, dtype, B, D), rnd(rng, dtype, B, D), rnd(rng, dtype, D), rnd(rng, dtype, 1)
-        X, G, LS = ld(x), ld(gy), ld(ls)
-        for sign in (1.0, -1.0):
-            F = np.exp(sign * LS)
-            Y = X * F
-
-            def run(off):
-                A = Arena(dtype, off)
-                dx, dg, dls, dgl = A.put(x), A.put(gy), A.put(ls), A.put(gld)
-                o_y, o_ld, o_gx, o_gls, o_gls0 = A.out(B, D), A.out(1), A.out(B, D), A.out(D), A.out(D)
-                inplace = A.put(x)
-                o_ld2, o_gls2 = A.out(1), A.out(D)
-                st = stream()
-                name = "zs_flow_scale_fwd" + sfx(dtype)
-                assert lib.raw(name, dx.data_ptr(), dls.data_ptr(), sign, o_y.data_ptr(), o_ld.data_ptr(), B, D, st) == 0
-                assert lib.raw(name, inplace.data_ptr(), dls.data_ptr(), sign, inplace.data_ptr(), o_ld2.data_ptr(), B, D, st) == 0
-                name = "zs_flow_scale_bwd" + sfx(dtype)
-                args = (dg.data_ptr(), o_y.data_ptr(), dls.data_ptr())
-                assert lib.raw(name, *args, dgl.data_ptr(), sign, o_gx.data_ptr(), o_gls.data_ptr(), B, D, st) == 0
-                assert lib.raw(name, *args, dgl.data_ptr(), sign, o_gx.data_ptr(), o_gls2.data_ptr(), B, D, st) == 0
-                assert lib.raw(name, *args, None, sign, o_gx.data_ptr(), o_gls0.data_ptr(), B, D, st) == 0
-                A.guards_intact()
-                within(o_y, Y, np.abs(Y), dtype)
-                assert torch.equal(inplace, o_y), "in place differs from out of place"
-                within(o_ld, LS.sum(), np.abs(LS).sum(), dtype, n=D)
-                assert torch.equal(o_ld, o_ld2) and torch.equal(o_gls, o_gls2), "a reduction is not reproducible"
-                within(o_gx, G * F, np.abs(G * F), dtype)
-                Yk = got(o_y)                      # the backward reads the SAVED output: the truth uses the same numbers
-                S = np.abs(G * Yk).sum(0)
-                within(o_gls, sign * (G * Yk).sum(0) + ld(gld)[0], S + abs(ld(gld)[0]), dtype, n=B + 1)
-                within(o_gls0, sign * (G * Yk).sum(0), S, dtype, n=B)
-                return [o_y, o_ld, o_gx, o_gls, o_gls0]
-            both_offsets(run)
+        check_scale(lib, dtype, B, D, rng)
 
 
 # ------------------------------------------------------------------------------------------------ MADE's affine
+def check_made(lib, dtype, B, D, rng):
+    """MADE's affine forward, backward and inverse column on one [B, D] problem drawn from `rng`, both layouts"""
+    x, gu, gld, net = rnd(rng, dtype, B, D), rnd(rng, dtype, B, D), rnd(rng, dtype, B, D), rnd(rng, dtype, B, 2 * D)
+    X, GU, GL, NET = ld(x), ld(gu), ld(gld), ld(net)
+    Mn, LA = NET[:, :D], NET[:, D:]
+    E = np.exp(-LA)
+    U = (X - Mn) * E
+    Su = (np.abs(X) + np.abs(Mn)) * E
+    col = D // 2
+
+    def run(off):
+        A = Arena(dtype, off)
+        dx, dgu, dgl, dnet = A.put(x), A.put(gu), A.put(gld), A.put(net)
+        o_u, o_ld, o_gx, o_gx2, o_inv = (A.out(B, D) for _ in range(5))
+        o_gnet, o_gnet2 = A.out(B, 2 * D), A.out(B, 2 * D)
+        o_inv.fill_(7.0)
+        st = stream()
+        assert lib.raw("zs_flow_made_fwd" + sfx(dtype), dx.data_ptr(), dnet.data_ptr(), o_u.data_ptr(), o_ld.data_ptr(), B, D, st) == 0
+        assert lib.raw("zs_flow_made_bwd" + sfx(dtype), dgu.data_ptr(), dgl.data_ptr(), dx.data_ptr(), dnet.data_ptr(),
+                       o_gx.data_ptr(), o_gnet.data_ptr(), B, D, st) == 0
+        assert lib.raw("zs_flow_made_bwd" + sfx(dtype), dgu.data_ptr(), None, dx.data_ptr(), dnet.data_ptr(),
+                       o_gx2.data_ptr(), o_gnet2.data_ptr(), B, D, st) == 0
+        assert lib.raw("zs_flow_made_inv_col" + sfx(dtype), dgu.data_ptr(), dnet.data_ptr(), o_inv.data_ptr(), B, D, col, st) == 0
+        A.guards_intact()
+        within(o_u, U, Su, dtype)
+        assert torch.equal(o_ld, -dnet[:, D:])
+        within(o_gx, GU * E, np.abs(GU * E), dtype)
+        within(o_gnet[:, :D], -GU * E, np.abs(GU * E), dtype)
+        within(o_gnet[:, D:], -(GU * U) - GL, np.abs(GU) * Su + np.abs(GL), dtype)
+        assert torch.equal(o_gx, o_gx2) and torch.equal(o_gnet[:, :D], o_gnet2[:, :D])
+        within(o_gnet2[:, D:], -(GU * U), np.abs(GU) * Su, dtype)
+        inv = GU[:, col] * np.exp(LA[:, col]) + Mn[:, col]
+        within(o_inv[:, col], inv, np.abs(GU[:, col] * np.exp(LA[:, col])) + np.abs(Mn[:, col]), dtype)
+        others = [c for c in range(D) if c != col]
+        assert bool((o_inv[:, others] == 7.0).all()), "another column was written"
+        return [o_u, o_ld, o_gx, o_gnet, o_inv]
+    both_offsets(run)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("B", BS)
 def test_made_affine_forward_backward_and_inverse_column(lib, dtype, B):
     rng = np.random.RandomState(41 + B)
     for D in DS_MADE:
-        x, gu, gld, net = rnd(rng, dtype, B, D), rnd(rng, dtype, B, D), rnd(rng, dtype, B, D), rnd(rng, dtype, B, 2 * D)
-        X, GU, GL, NET = ld(x), ld(gu), ld(gld), ld(net)
-        Mn, LA = NET[:, :D], NET[:, D:]
-        E = np.exp(-LA)
-        U = (X - Mn) * E
-        Su = (np.abs(X) + np.abs(Mn)) * E
-        col = D // 2
-
-        def run(off):
-            A = Arena(dtype, off)
-            dx, dgu, dgl, dnet = A.put(x), A.put(gu), A.put(gld), A.put(net)
-            o_u, o_ld, o_gx, o_gx2, o_inv = (A.out(B, D) for _ in range(5))
-            o_gnet, o_gnet2 = A.out(B, 2 * D), A.out(B, 2 * D)
-            o_inv.fill_(7.0)
-            st = stream()
-            assert lib.raw("zs_flow_made_fwd" + sfx(dtype), dx.data_ptr(), dnet.data_ptr(), o_u.data_ptr(), o_ld.data_ptr(), B, D, st) == 0
-            assert lib.raw("zs_flow_made_bwd" + sfx(dtype), dgu.data_ptr(), dgl.data_ptr(), dx.data_ptr(), dnet.data_ptr(),
-                           o_gx.data_ptr(), o_gnet.data_ptr(), B, D, st) == 0
-            assert lib.raw("zs_flow_made_bwd" + sfx(dtype), dgu.data_ptr(), None, dx.data_ptr(), dnet.data_ptr(),
-                           o_gx2.data_ptr(), o_gnet2.data_ptr(), B, D, st) == 0
-            assert lib.raw("zs_flow_made_inv_col" + sfx(dtype), dgu.data_ptr(), dnet.data_ptr(), o_inv.data_ptr(), B, D, col, st) == 0
-            A.guards_intact()
-            within(o_u, U, Su, dtype)
-            assert torch.equal(o_ld, -dnet[:, D:])
-            within(o_gx, GU * E, np.abs(GU * E), dtype)
-            within(o_gnet[:, :D], -GU * E, np.abs(GU * E), dtype)
-            within(o_gnet[:, D:], -(GU * U) - GL, np.abs(GU) * Su + np.abs(GL), dtype)
-            assert torch.equal(o_gx, o_gx2) and torch.equal(o_gnet[:, :D], o_gnet2[:, :D])
-            within(o_gnet2[:, D:], -(GU * U), np.abs(GU) * Su, dtype)
-            inv = GU[:, col] * np.exp(LA[:, col]) + Mn[:, col]
-            within(o_inv[:, col], inv, np.abs(GU[:, col] * np.exp(LA[:, col])) + np.abs(Mn[:, col]), dtype)
-            others = [c for c in range(D) if c != col]
-            assert bool((o_inv[:, others] == 7.0).all()), "another column was written"
-            return [o_u, o_ld, o_gx, o_gnet, o_inv]
-        both_offsets(run)
+        check_made(lib, dtype, B, D, rng)
 
 
 # ------------------------------------------------------------------------------------------------ FlowDistribution tail
@@ -280,46 +300,52 @@ def base_truth(base, Z, LOC, SC):
     return -(at + sp) - np.log(SC), at + sp + np.abs(np.log(SC)), -(np.tanh(t / 2) / SC)
 
 
+def check_tail(lib, dtype, B, D, base, rng):
+    """The tail's forward (three logdet kinds) and backward on one [B, D] problem drawn from `rng`, parameters per column and
+    per element, both layouts"""
+    for param_rows in (0, 1):
+        pshape = (B, D) if param_rows else (D,)
+        z, g = rnd(rng, dtype, B, D), rnd(rng, dtype, B)
+        loc = rnd(rng, dtype, *pshape)
+        scale = torch.from_numpy(np.exp(0.5 * rng.standard_normal(pshape))).to(dtype).double().numpy()
+        lds, ldr = rnd(rng, dtype, 1), rnd(rng, dtype, B)
+        Z, G, LOC, SC = ld(z), ld(g), ld(loc), ld(scale)
+        lp, S, dz = base_truth(base, Z, LOC, SC)
+
+        def run(off):
+            A = Arena(dtype, off)
+            dz_, dg, dloc, dsc, dlds, dldr = A.put(z), A.put(g), A.put(loc), A.put(scale), A.put(lds), A.put(ldr)
+            o_n, o_s, o_r, o_r2, o_gl = (A.out(B) for _ in range(5))
+            o_gz, o_gz2 = A.out(B, D), A.out(B, D)
+            st = stream()
+            name = "zs_flow_tail" + sfx(dtype)
+            head = (base, dz_.data_ptr(), dloc.data_ptr(), dsc.data_ptr(), param_rows)
+            assert lib.raw(name, *head, None, NONE, o_n.data_ptr(), B, D, st) == 0
+            assert lib.raw(name, *head, dlds.data_ptr(), SCALAR, o_s.data_ptr(), B, D, st) == 0
+            assert lib.raw(name, *head, dldr.data_ptr(), ROWS, o_r.data_ptr(), B, D, st) == 0
+            assert lib.raw(name, *head, dldr.data_ptr(), ROWS, o_r2.data_ptr(), B, D, st) == 0
+            name = "zs_flow_tail_bwd" + sfx(dtype)
+            head = (base, dg.data_ptr(), dz_.data_ptr(), dloc.data_ptr(), dsc.data_ptr(), param_rows)
+            assert lib.raw(name, *head, o_gz.data_ptr(), o_gl.data_ptr(), B, D, st) == 0
+            assert lib.raw(name, *head, o_gz2.data_ptr(), None, B, D, st) == 0
+            A.guards_intact()
+            within(o_n, lp.sum(1), S.sum(1), dtype, n=D)
+            within(o_s, lp.sum(1) + ld(lds)[0], S.sum(1) + abs(ld(lds)[0]), dtype, n=D + 1)
+            within(o_r, lp.sum(1) + ld(ldr), S.sum(1) + np.abs(ld(ldr)), dtype, n=D + 1)
+            assert torch.equal(o_r, o_r2), "the row reduction is not reproducible"
+            within(o_gz, G[:, None] * dz, np.abs(G[:, None] * dz), dtype)
+            assert torch.equal(o_gz, o_gz2) and torch.equal(o_gl, dg)
+            return [o_n, o_s, o_r, o_gz, o_gl]
+        both_offsets(run)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("B", BS)
 @pytest.mark.parametrize("base", [NORMAL, LOGISTIC], ids=["normal", "logistic"])
 def test_tail_forward_and_backward(lib, dtype, B, base):
     rng = np.random.RandomState(53 + B + base)
     for D in DS:
-        for param_rows in (0, 1):
-            pshape = (B, D) if param_rows else (D,)
-            z, g = rnd(rng, dtype, B, D), rnd(rng, dtype, B)
-            loc = rnd(rng, dtype, *pshape)
-            scale = torch.from_numpy(np.exp(0.5 * rng.standard_normal(pshape))).to(dtype).double().numpy()
-            lds, ldr = rnd(rng, dtype, 1), rnd(rng, dtype, B)
-            Z, G, LOC, SC = ld(z), ld(g), ld(loc), ld(scale)
-            lp, S, dz = base_truth(base, Z, LOC, SC)
-
-            def run(off):
-                A = Arena(dtype, off)
-                dz_, dg, dloc, dsc, dlds, dldr = A.put(z), A.put(g), A.put(loc), A.put(scale), A.put(lds), A.put(ldr)
-                o_n, o_s, o_r, o_r2, o_gl = (A.out(B) for _ in range(5))
-                o_gz, o_gz2 = A.out(B, D), A.out(B, D)
-                st = stream()
-                name = "zs_flow_tail" + sfx(dtype)
-                head = (base, dz_.data_ptr(), dloc.data_ptr(), dsc.data_ptr(), param_rows)
-                assert lib.raw(name, *head, None, NONE, o_n.data_ptr(), B, D, st) == 0
-                assert lib.raw(name, *head, dlds.data_ptr(), SCALAR, o_s.data_ptr(), B, D, st) == 0
-                assert lib.raw(name, *head, dldr.data_ptr(), ROWS, o_r.data_ptr(), B, D, st) == 0
-                assert lib.raw(name, *head, dldr.data_ptr(), ROWS, o_r2.data_ptr(), B, D, st) == 0
-                name = "zs_flow_tail_bwd" + sfx(dtype)
-                head = (base, dg.data_ptr(), dz_.data_ptr(), dloc.data_ptr(), dsc.data_ptr(), param_rows)
-                assert lib.raw(name, *head, o_gz.data_ptr(), o_gl.data_ptr(), B, D, st) == 0
-                assert lib.raw(name, *head, o_gz2.data_ptr(), None, B, D, st) == 0
-                A.guards_intact()
-                within(o_n, lp.sum(1), S.sum(1), dtype, n=D)
-                within(o_s, lp.sum(1) + ld(lds)[0], S.sum(1) + abs(ld(lds)[0]), dtype, n=D + 1)
-                within(o_r, lp.sum(1) + ld(ldr), S.sum(1) + np.abs(ld(ldr)), dtype, n=D + 1)
-                assert torch.equal(o_r, o_r2), "the row reduction is not reproducible"
-                within(o_gz, G[:, None] * dz, np.abs(G[:, None] * dz), dtype)
-                assert torch.equal(o_gz, o_gz2) and torch.equal(o_gl, dg)
-                return [o_n, o_s, o_r, o_gz, o_gl]
-            both_offsets(run)
+        check_tail(lib, dtype, B, D, base, rng)
 
 
 # ------------------------------------------------------------------------------------------------ edges

@@ -202,6 +202,7 @@ def check_kind(lib, dtype, kind, C, rows, seed, shifts=(0, 1)):
     else:
         Sp = P.abs() + (h * G).abs()
         check_kinetic(ksum, (P + h * G) ** 2, Sp * Sp, C, rows, dtype)
+    return data, outs[0]
 
 
 # ------------------------------------------------------------------------------------------------ 1. moves
@@ -334,10 +335,10 @@ def close40(got, want, scale=None):
     assert bool((err <= 2.0 ** -40 * scale + 1e-300).all()), float((err / scale.clamp_min(1e-300)).max())
 
 
-@pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
-@pytest.mark.parametrize("C", [1, 3, 65, 257])
-def test_decide_matches_the_double_restatement_and_isolates_non_finite_chains(lib, C, dtype):
-    k, l0, l1, u = decide_inputs(C, DECIDE_SEEDS[C])
+def check_decide(lib, dtype, C, seed):
+    """One adapting decide of C chains on decide_inputs(C, seed) against the float64 restatement: all five `out` rows, `accept`
+    outside the guard, and the whole state block (step size, averages, ABAR, NACC); returns (k, l0, l1, u, t, out, acc, st)."""
+    k, l0, l1, u = decide_inputs(C, seed)
     l0, l1, u = [t.to(dtype) for t in (l0, l1, u)]          # what the kernel is given
     st0 = [EPS, EPS, 0., 0., 0., 0., 0., 0.]
     t = decide_truth(k, l0, l1, u, st0, True)
@@ -353,6 +354,13 @@ def test_decide_matches_the_double_restatement_and_isolates_non_finite_chains(li
     assert torch.equal(out[4], torch.where(acc.bool(), l1.double(), l0.double()))
     close40(st[:7], torch.tensor(t["st"][:7], dtype=F64), torch.tensor([1 + abs(x) for x in t["st"][:7]], dtype=F64))
     assert float(st[7]) == float(acc.sum())
+    return k, l0, l1, u, t, out, acc, st
+
+
+@pytest.mark.parametrize("dtype", [F32, F64], ids=["f32", "f64"])
+@pytest.mark.parametrize("C", [1, 3, 65, 257])
+def test_decide_matches_the_double_restatement_and_isolates_non_finite_chains(lib, C, dtype):
+    k, l0, l1, u, t, out, acc, st = check_decide(lib, dtype, C, DECIDE_SEEDS[C])
     # a second adapting decide, then a frozen one, on the block the first one left
     dev_state = st.to(DEV)
     _, _, st2 = run_decide(lib, dtype, C, k, l0, l1, u, dev_state, adapting=1)

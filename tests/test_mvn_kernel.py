@@ -216,82 +216,91 @@ def lower_of(gt, R, D):
 
 
 # ------------------------------------------------------------------------------------------------ the grid
+def check_forward_and_backward(lib, D, R, K, dtypes=(F32, F64), shifts=(0, 1), d=None):
+    """Every entry point on one shape (inputs `d`, by default case_inputs(D, R, K)) against the float64 truths and the derived
+    bounds; returns {dtype: [z, lp1, lp2, lpz, gx, gm2, gt2, gx1, gm0, gt0, gm1, gt1]} (CPU) of the first layout in `shifts`."""
+    d = case_inputs(D, R, K) if d is None else d
+    mean, tril, x, eps, g, gz = d["mean"], d["tril"], d["x"], d["eps"], d["g"], d["gz"]
+    ones = torch.ones_like(g)
+    tz, tlp1 = mvn_host.reference_sample(mean, tril, eps)
+    ty = mvn_host.reference_whiten(mean, tril, x)
+    tlp2 = mvn_host.reference_density(tril, ty)
+    tw, tgm2, tgt2 = mvn_host.reference_score(tril, ty, g)
+    tw1, tgm1, tgt1 = mvn_host.reference_score(tril, eps, g)
+    tgm0, tgt0 = mvn_host.reference_sample_bwd(tril, eps, gz, g)
+    found = {}
+    for dtype in dtypes:
+        res = []
+        for shift in shifts:
+            ar = Arena(shift)
+            dm, dt, dx, de = ar.put(mean, dtype), ar.put(tril, dtype), ar.put(x, dtype), ar.put(eps, dtype)
+            dg, dgz, d1 = ar.put(g, dtype), ar.put(gz, dtype), ar.put(ones, dtype)
+            outs, twice = [], []
+            for rep in range(2):          # the same calls again: the same bits
+                o = []
+                rc, z, lp1 = v1(lib, dtype, ar, dm, dt, de, K, R, D)
+                o += [rc, z, lp1]
+                rc, lp2 = v2(lib, dtype, ar, dm, dt, dx, K, R, D)
+                o += [rc, lp2]
+                rc, lpz = v2(lib, dtype, ar, dm, dt, z, K, R, D)
+                o += [rc, lpz]
+                o += list(v2b(lib, dtype, ar, dm, dt, dx, dg, K, R, D))
+                o += list(v2b(lib, dtype, ar, dm, dt, dx, d1, K, R, D))[:2]
+                o += list(v1b(lib, dtype, ar, dt, de, dgz, dg, 1, K, R, D))
+                o += list(v1b(lib, dtype, ar, dt, de, None, dg, 0, K, R, D))
+                (outs if rep == 0 else twice).extend(o)
+            torch.cuda.synchronize()
+            ar.check_guards()
+            for a, b in zip(outs, twice):
+                if isinstance(a, int):
+                    assert a == 0 and b == 0
+                else:
+                    assert same_bits(a, b), "two identical calls differ (D=%d R=%d K=%d)" % (D, R, K)
+            res.append([a.cpu() for a in outs if not isinstance(a, int)])
+        for a, b in zip(res[0], res[-1]):
+            assert same_bits(a, b), "the aligned and the shifted layout differ (D=%d R=%d K=%d)" % (D, R, K)
+        found[dtype] = res[0]
+        z, lp1, lp2, lpz, gx, gm2, gt2, gx1, gm0, gt0, gm1, gt1 = res[0]
+        B = Bounds(dtype, mean, tril, K)
+        tag = " [D=%d R=%d K=%d %s]" % (D, R, K, sfx(dtype))
+        # V1
+        assert_close("V1 z" + tag, z.view(K, R, D), tz, B.z(eps))
+        assert_close("V1 lp" + tag, lp1.view(K, R), tlp1, B.lp(eps))
+        # V2
+        e = B.e_y(x, ty)
+        assert_close("V2 lp" + tag, lp2.view(K, R), tlp2, B.lp(ty, e))
+        # V2 at V1's own draw against V1's lp: within the sum of the two bounds
+        zd = z.view(K, R, D).to(F64)
+        yz = mvn_host.reference_whiten(mean, tril, zd)
+        assert_close("V2 at V1's z" + tag, lpz.view(K, R), lp1.view(K, R).to(F64), B.lp(eps) + B.lp(yz, B.e_y(zd, yz)))
+        # back substitution, read back through gx with glp = 1
+        ew = B.e_w(tw, e)
+        assert_close("w" + tag, -gx1.view(K, R, D).to(F64), tw, ew)
+        assert_close("V2 gx" + tag, gx.view(K, R, D), -g[..., None] * tw, g.abs()[..., None] * ew + B.u * (g[..., None] * tw).abs())
+        # gradients
+        tolm, tolt = B.score(g, tw, ty, e, ew)
+        assert_close("V2 gmean" + tag, gm2.view(R, D), tgm2, tolm)
+        low, zero = lower_of(gt2, R, D)
+        assert zero, "gtril's upper triangle is not exactly zero"
+        assert_close("V2 gtril" + tag, low, tgt2, tolt)
+        ew1 = B.e_w(tw1, torch.zeros_like(eps))
+        tolm, tolt = B.score(g, tw1, eps, torch.zeros_like(eps), ew1)
+        assert_close("V1 gmean (detached draw)" + tag, gm1.view(R, D), tgm1, tolm)
+        low, zero = lower_of(gt1, R, D)
+        assert zero, "gtril's upper triangle is not exactly zero"
+        assert_close("V1 gtril (detached draw)" + tag, low, tgt1, tolt)
+        tolm, tolt = B.reparam(gz, eps, g)
+        assert_close("V1 gmean" + tag, gm0.view(R, D), tgm0, tolm)
+        low, zero = lower_of(gt0, R, D)
+        assert zero, "gtril's upper triangle is not exactly zero"
+        assert_close("V1 gtril" + tag, low, tgt0, tolt)
+    return found
+
+
 @pytest.mark.parametrize("D", DS)
 def test_forward_and_backward_against_float64(lib, D):
     for R, K in grid(D):
-        d = case_inputs(D, R, K)
-        mean, tril, x, eps, g, gz = d["mean"], d["tril"], d["x"], d["eps"], d["g"], d["gz"]
-        ones = torch.ones_like(g)
-        tz, tlp1 = mvn_host.reference_sample(mean, tril, eps)
-        ty = mvn_host.reference_whiten(mean, tril, x)
-        tlp2 = mvn_host.reference_density(tril, ty)
-        tw, tgm2, tgt2 = mvn_host.reference_score(tril, ty, g)
-        tw1, tgm1, tgt1 = mvn_host.reference_score(tril, eps, g)
-        tgm0, tgt0 = mvn_host.reference_sample_bwd(tril, eps, gz, g)
-        for dtype in (F32, F64):
-            res = []
-            for shift in (0, 1):
-                ar = Arena(shift)
-                dm, dt, dx, de = ar.put(mean, dtype), ar.put(tril, dtype), ar.put(x, dtype), ar.put(eps, dtype)
-                dg, dgz, d1 = ar.put(g, dtype), ar.put(gz, dtype), ar.put(ones, dtype)
-                outs, twice = [], []
-                for rep in range(2):          # the same calls again: the same bits
-                    o = []
-                    rc, z, lp1 = v1(lib, dtype, ar, dm, dt, de, K, R, D)
-                    o += [rc, z, lp1]
-                    rc, lp2 = v2(lib, dtype, ar, dm, dt, dx, K, R, D)
-                    o += [rc, lp2]
-                    rc, lpz = v2(lib, dtype, ar, dm, dt, z, K, R, D)
-                    o += [rc, lpz]
-                    o += list(v2b(lib, dtype, ar, dm, dt, dx, dg, K, R, D))
-                    o += list(v2b(lib, dtype, ar, dm, dt, dx, d1, K, R, D))[:2]
-                    o += list(v1b(lib, dtype, ar, dt, de, dgz, dg, 1, K, R, D))
-                    o += list(v1b(lib, dtype, ar, dt, de, None, dg, 0, K, R, D))
-                    (outs if rep == 0 else twice).extend(o)
-                torch.cuda.synchronize()
-                ar.check_guards()
-                for a, b in zip(outs, twice):
-                    if isinstance(a, int):
-                        assert a == 0 and b == 0
-                    else:
-                        assert same_bits(a, b), "two identical calls differ (D=%d R=%d K=%d)" % (D, R, K)
-                res.append([a.cpu() for a in outs if not isinstance(a, int)])
-            for a, b in zip(*res):
-                assert same_bits(a, b), "the aligned and the shifted layout differ (D=%d R=%d K=%d)" % (D, R, K)
-            z, lp1, lp2, lpz, gx, gm2, gt2, gx1, gm0, gt0, gm1, gt1 = res[0]
-            B = Bounds(dtype, mean, tril, K)
-            tag = " [D=%d R=%d K=%d %s]" % (D, R, K, sfx(dtype))
-            # V1
-            assert_close("V1 z" + tag, z.view(K, R, D), tz, B.z(eps))
-            assert_close("V1 lp" + tag, lp1.view(K, R), tlp1, B.lp(eps))
-            # V2
-            e = B.e_y(x, ty)
-            assert_close("V2 lp" + tag, lp2.view(K, R), tlp2, B.lp(ty, e))
-            # V2 at V1's own draw against V1's lp: within the sum of the two bounds
-            zd = z.view(K, R, D).to(F64)
-            yz = mvn_host.reference_whiten(mean, tril, zd)
-            assert_close("V2 at V1's z" + tag, lpz.view(K, R), lp1.view(K, R).to(F64), B.lp(eps) + B.lp(yz, B.e_y(zd, yz)))
-            # back substitution, read back through gx with glp = 1
-            ew = B.e_w(tw, e)
-            assert_close("w" + tag, -gx1.view(K, R, D).to(F64), tw, ew)
-            assert_close("V2 gx" + tag, gx.view(K, R, D), -g[..., None] * tw, g.abs()[..., None] * ew + B.u * (g[..., None] * tw).abs())
-            # gradients
-            tolm, tolt = B.score(g, tw, ty, e, ew)
-            assert_close("V2 gmean" + tag, gm2.view(R, D), tgm2, tolm)
-            low, zero = lower_of(gt2, R, D)
-            assert zero, "gtril's upper triangle is not exactly zero"
-            assert_close("V2 gtril" + tag, low, tgt2, tolt)
-            ew1 = B.e_w(tw1, torch.zeros_like(eps))
-            tolm, tolt = B.score(g, tw1, eps, torch.zeros_like(eps), ew1)
-            assert_close("V1 gmean (detached draw)" + tag, gm1.view(R, D), tgm1, tolm)
-            low, zero = lower_of(gt1, R, D)
-            assert zero, "gtril's upper triangle is not exactly zero"
-            assert_close("V1 gtril (detached draw)" + tag, low, tgt1, tolt)
-            tolm, tolt = B.reparam(gz, eps, g)
-            assert_close("V1 gmean" + tag, gm0.view(R, D), tgm0, tolm)
-            low, zero = lower_of(gt0, R, D)
-            assert zero, "gtril's upper triangle is not exactly zero"
-            assert_close("V1 gtril" + tag, low, tgt0, tolt)
+        check_forward_and_backward(lib, D, R, K)
     print("worst error / tolerance so far: %s" % ", ".join("%s %.3f" % kv for kv in sorted(WORST.items())))
 
 
