@@ -19,6 +19,8 @@ from .graph import GraphedStep, GraphedStages
 from .framework.stochastic_tensor import skip_discarded_draws
 from .layers import particle_linear, particle_mlp, particle_rmse, Linear, Sequential
 from . import optim
+from . import transform
+from .transform import PlanarFlow, HouseholderFlow
 
 
 def is_loglikelihood(generator, variational, observed, axis=0):
