@@ -1,4 +1,4 @@
-// The arithmetic and the lane-group maps of the categorical kernels (csrc/zs_cat_math.h with zs_flat_math.h: __host__ __device__)
+// The arithmetic and the lane-group maps of the categorical kernels (csrc/zs_cat_math.h with zs_group_math.h: __host__ __device__)
 // compiled for the HOST and run under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_cat_host_math.py):
 //     hipcc -x hip --cuda-host-only -Xarch_host -fsanitize=address,undefined ...
 // (1) the Gumbel transform at the smallest and the largest u01 and over the range between, finite and against long double;
@@ -7,7 +7,8 @@
 //     a long-double logsumexp for every N of tests/test_cat_kernel.py, logits at scale 0 / 1 / 5, offset by +-80, with a -inf
 //     entry and all -inf; also the merges in the opposite operand order (every lane's pair must agree to the bound);
 // (3) the lane-group map for every N of the kernel test and R in {1, 3, 65}: each (row, category) is owned by exactly one
-//     (block, thread, chunk, element) of the kernels' own loops (cat_place, cat_chunk_first, cat_chunk_step), over exactly-sized heap arrays;
+//     (block, thread, chunk, element) of the kernels' own loops (group_place, cat_item_first / step, cat_chunk_first / step), over
+//     exactly-sized heap arrays;
 // (4) the densities at tau in {1e-3, 1e3} and between against long double.   Prints "cat host math ok: N checks".
 #include <math.h>
 #include <stdio.h>
@@ -16,26 +17,10 @@
 #include <vector>
 
 #include "../../zhusuan-pytorch_amd/csrc/zs_cat_math.h"
+#include "zs_host_check.h"
 
-static long n_checks = 0;
-static int n_fail = 0;
-static void expect(bool ok, const char* what, double got, double want) {
-  ++n_checks;
-  if (!ok) {
-    if (n_fail < 20) fprintf(stderr, "FAIL %s: got %.17g want %.17g\n", what, got, want);
-    ++n_fail;
-  }
-}
-typedef long double ld;
 template <typename T> static ld eps_elem() { return sizeof(T) == 4 ? ldexpl(1.0L, -20) : ldexpl(1.0L, -48); }
 template <typename T> static ld eps_sum(ld n) { return sizeof(T) == 4 ? ldexpl(1.0L, -20) + n * ldexpl(1.0L, -24) : ldexpl(1.0L, -48) + n * ldexpl(1.0L, -53); }
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static double uniform01() {          // xorshift64*: strictly inside (0, 1)
-  rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
-  return ((double)((rng_state * 0x2545F4914F6CDD1Dull) >> 11) + 0.5) * ldexp(1.0, -53);
-}
-static double normal01() { return sqrt(-2.0 * log(uniform01())) * cos(6.283185307179586 * uniform01()); }
 
 // ---------------------------------------------------------------- (1)
 template <typename T>
@@ -74,11 +59,8 @@ static zs::CatMS<T> row_pair(const T* row, int64_t N, bool flip, int take) {
     }
     lane[g] = ms;
   }
-  for (int o = G >> 1; o > 0; o >>= 1) {
-    std::vector<zs::CatMS<T>> next(G);
-    for (int g = 0; g < G; ++g) next[g] = flip ? zs::cat_ms_merge(lane[g ^ o], lane[g]) : zs::cat_ms_merge(lane[g], lane[g ^ o]);
-    lane = next;
-  }
+  if (flip) zs::group_butterfly_host(lane.data(), G, [](const zs::CatMS<T>& a, const zs::CatMS<T>& b) { return zs::cat_ms_merge(b, a); });
+  else zs::group_butterfly_host(lane.data(), G, [](const zs::CatMS<T>& a, const zs::CatMS<T>& b) { return zs::cat_ms_merge(a, b); });
   return lane[take % G];
 }
 
@@ -123,11 +105,11 @@ static void check_lane_groups() {
     for (int64_t R : Rs) for (int grid = 1; grid <= 3; grid += 2) {
       unsigned char* owned = (unsigned char*)calloc((size_t)(R * N), 1);
       for (int b = 0; b < grid; ++b) for (int tid = 0; tid < THREADS; ++tid) {
-        const zs::CatPlace pl = zs::cat_place(b, tid, grid, G);          // what the kernels call
-        expect(pl.g >= 0 && pl.g < G && pl.first % G == 0 && pl.first + G <= 64 && ((tid & 63) - pl.first) == pl.g,
-               "a group stays inside its wave", pl.first, pl.g);
-        for (int64_t it = pl.item; it < R; it += pl.stride)
-          for (int64_t j0 = zs::cat_chunk_first(pl.g); j0 < N; j0 += zs::cat_chunk_step(G))
+        const zs::GroupPlace pl = zs::group_place(tid, THREADS, G);          // what the kernels call
+        expect(pl.lane >= 0 && pl.lane < G && pl.first % G == 0 && pl.first + G <= 64 && ((tid & 63) - pl.first) == pl.lane,
+               "a group stays inside its wave", pl.first, pl.lane);
+        for (int64_t it = zs::cat_item_first(b, pl); it < R; it += zs::cat_item_step(grid, pl))
+          for (int64_t j0 = zs::cat_chunk_first(pl.lane); j0 < N; j0 += zs::cat_chunk_step(G))
             for (int c = 0; c < 4; ++c)
               if (j0 + c < N) ++owned[it * N + j0 + c];
       }
@@ -224,10 +206,5 @@ int main() {
   check_lane_groups();
   check_densities<float>();
   check_densities<double>();
-  if (n_fail) {
-    fprintf(stderr, "%d of %ld checks failed\n", n_fail, n_checks);
-    return 1;
-  }
-  printf("cat host math ok: %ld checks\n", n_checks);
-  return 0;
+  return finish("cat host math ok");
 }

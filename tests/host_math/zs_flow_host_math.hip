@@ -12,17 +12,8 @@
 #include <vector>
 
 #include "../../zhusuan-pytorch_amd/csrc/zs_flow_math.h"
+#include "zs_host_check.h"
 
-static long n_checks = 0;
-static int n_fail = 0;
-static void expect(bool ok, const char* what, double got, double want) {
-  ++n_checks;
-  if (!ok) {
-    if (n_fail < 20) fprintf(stderr, "FAIL %s: got %.17g want %.17g\n", what, got, want);
-    ++n_fail;
-  }
-}
-typedef long double ld;
 template <typename T> static ld rel_bound() { return sizeof(T) == 4 ? ldexpl(1.0L, -20) : ldexpl(1.0L, -48); }
 // results below the normal range of T carry an absolute, not a relative, rounding error: not held to the relative bound
 template <typename T> static bool representable(ld want) { return want == 0 || fabsl(want) > (sizeof(T) == 4 ? 1e-30L : 1e-290L); }
@@ -171,10 +162,5 @@ int main() {
   check_tail<float>();
   check_tail<double>();
   check_index_maps();
-  if (n_fail) {
-    fprintf(stderr, "flow host math: %d of %ld checks failed\n", n_fail, n_checks);
-    return 1;
-  }
-  printf("flow host math ok: %ld checks\n", n_checks);
-  return 0;
+  return finish("flow host math ok");
 }

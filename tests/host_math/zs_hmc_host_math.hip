@@ -15,17 +15,8 @@
 #include <vector>
 
 #include "../../zhusuan-pytorch_amd/csrc/zs_hmc_math.h"
+#include "zs_host_check.h"
 
-static long n_checks = 0;
-static int n_fail = 0;
-static void expect(bool ok, const char* what, double got, double want) {
-  ++n_checks;
-  if (!ok) {
-    if (n_fail < 20) fprintf(stderr, "FAIL %s: got %.17g want %.17g\n", what, got, want);
-    ++n_fail;
-  }
-}
-typedef long double ld;
 template <typename T> static ld rel_bound() { return sizeof(T) == 4 ? ldexpl(1.0L, -20) : ldexpl(1.0L, -48); }
 template <typename T>
 static void near(T got, ld want, ld S, const char* what) {
@@ -212,10 +203,5 @@ int main() {
     walk_layout(C, std::vector<int64_t>(32, 4));
     walk_layout(C, {1023, 1025, 2, 2047});
   }
-  if (n_fail) {
-    fprintf(stderr, "%d of %ld checks FAILED\n", n_fail, n_checks);
-    return 1;
-  }
-  printf("hmc host math ok: %ld checks\n", n_checks);
-  return 0;
+  return finish("hmc host math ok");
 }

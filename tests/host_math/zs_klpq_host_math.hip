@@ -1,4 +1,4 @@
-// The arithmetic and the lane map of the inclusive-KL kernels (csrc/zs_klpq_math.h with zs_flat_math.h: __host__ __device__)
+// The arithmetic and the lane map of the inclusive-KL kernels (csrc/zs_klpq_math.h with zs_group_math.h: __host__ __device__)
 // compiled for the HOST and run under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_klpq_host_math.py):
 //     hipcc -x hip --cuda-host-only -Xarch_host -fsanitize=address,undefined ...
 // (1) a datapoint's reductions in the kernel's split order -- each lane's partial over k = j, j + G, ..., then the xor butterfly --
@@ -20,27 +20,11 @@
 #include <vector>
 
 #include "../../zhusuan-pytorch_amd/csrc/zs_klpq_math.h"
+#include "zs_host_check.h"
 
 using namespace zs;
 
-static long n_checks = 0;
-static int n_fail = 0;
-static void expect(bool ok, const char* what, double got, double want) {
-  ++n_checks;
-  if (!ok) {
-    if (n_fail < 20) fprintf(stderr, "FAIL %s: got %.17g want %.17g\n", what, got, want);
-    ++n_fail;
-  }
-}
-typedef long double ld;
 template <typename T> static ld unit() { return sizeof(T) == 4 ? ldexpl(1.0L, -24) : ldexpl(1.0L, -53); }
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static double uniform01() {          // xorshift64*: strictly inside (0, 1)
-  rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
-  return ((double)((rng_state * 0x2545F4914F6CDD1Dull) >> 11) + 0.5) * ldexp(1.0, -53);
-}
-static double normal01() { return sqrt(-2.0 * log(uniform01())) * cos(6.283185307179586 * uniform01()); }
 
 static const int Ks[] = {1, 2, 3, 5, 31, 32, 33, 50, 63, 64, 65, 130, 257};
 static const int Bs[] = {1, 3, 65, 257};
@@ -63,7 +47,7 @@ template <typename T> struct Row { T m, s, bound, cost, sq; };
 // one datapoint as its group computes it: lanes 0 .. G - 1 in turn, then the butterflies
 template <typename T>
 static Row<T> group_forward(const KlpqSide& p, const KlpqSide& q, int64_t b, int64_t K, bool model_grad, T* wrow) {
-  const int G = klpq_group_lanes(K);
+  const int G = group_lanes(K);
   T v[ZS_KLPQ_WAVE], c[ZS_KLPQ_WAVE];
   KlpqParticle<T> first[ZS_KLPQ_WAVE];
   for (int j = 0; j < G; ++j) {
@@ -71,12 +55,12 @@ static Row<T> group_forward(const KlpqSide& p, const KlpqSide& q, int64_t b, int
     if (j < K) first[j] = klpq_particle<T>(p, q, j, b);
     v[j] = klpq_lane_max<T>(p, q, b, j, G, K, first[j]);
   }
-  klpq_butterfly_host(v, G, [](T a, T x) { return klpq_max(a, x); });
+  group_butterfly_host(v, G, [](T a, T x) { return group_fmax(a, x); });
   for (int j = 1; j < G; ++j) expect(memcmp(&v[j], &v[0], sizeof(T)) == 0, "the butterfly leaves one max in every lane", (double)v[j], (double)v[0]);
   Row<T> r;
   r.m = v[0];
   for (int j = 0; j < G; ++j) v[j] = klpq_lane_sumexp<T>(p, q, b, j, G, K, first[j], r.m);
-  klpq_butterfly_host(v, G, [](T a, T x) { return a + x; });
+  group_butterfly_host(v, G, [](T a, T x) { return a + x; });
   for (int j = 1; j < G; ++j) expect(memcmp(&v[j], &v[0], sizeof(T)) == 0, "the butterfly leaves one sum in every lane", (double)v[j], (double)v[0]);
   r.s = v[0];
   r.bound = klpq_bound(r.m, r.s, (T)log((double)K));
@@ -85,8 +69,8 @@ static Row<T> group_forward(const KlpqSide& p, const KlpqSide& q, int64_t b, int
     v[j] = a.cost;
     c[j] = a.sq;
   }
-  klpq_butterfly_host(v, G, [](T a, T x) { return a + x; });
-  klpq_butterfly_host(c, G, [](T a, T x) { return a + x; });
+  group_butterfly_host(v, G, [](T a, T x) { return a + x; });
+  group_butterfly_host(c, G, [](T a, T x) { return a + x; });
   r.cost = -v[0];
   r.sq = c[0];
   return r;
@@ -139,16 +123,16 @@ static void check_reductions() {
 
 // ---------------------------------------------------------------- (2)
 static void walk_map(int64_t K, int64_t B, int threads, int blocks) {
-  const int G = klpq_group_lanes(K);
+  const int G = group_lanes(K);
   int* own = heap<int>((size_t)(K * B), 0);
   expect(G >= 1 && G <= ZS_KLPQ_WAVE && (G & (G - 1)) == 0 && (K <= G || G == ZS_KLPQ_WAVE) && (G < 2 * K), "group lanes", G, (double)K);
   for (int blk = 0; blk < blocks; ++blk) for (int th = 0; th < threads; ++th) {
-    const KlpqPlace pl = klpq_place(th, threads, G);
-    if (blk == 0) expect((th - pl.j) / ZS_KLPQ_WAVE == (th - pl.j + G - 1) / ZS_KLPQ_WAVE && pl.grp < pl.groups, "a group inside its wave", th, G);
-    for (int64_t rb = klpq_row_first(blk, pl); rb < B; rb += klpq_row_step(blocks, pl)) {
+    const GroupPlace pl = group_place(th, threads, G);
+    if (blk == 0) expect((th - pl.lane) / ZS_KLPQ_WAVE == (th - pl.lane + G - 1) / ZS_KLPQ_WAVE && pl.grp < pl.groups, "a group inside its wave", th, G);
+    for (int64_t rb = group_row_first(blk, pl); rb < B; rb += group_row_step(blocks, pl)) {
       const int64_t b = rb + pl.grp;
       if (b >= B) continue;
-      for (int64_t k = pl.j; k < K; k += G) ++own[b * K + k];
+      for (int64_t k = pl.lane; k < K; k += G) ++own[b * K + k];
     }
   }
   bool once = true;
@@ -158,7 +142,7 @@ static void walk_map(int64_t K, int64_t B, int threads, int blocks) {
 }
 static void check_map() {
   for (int K : Ks) for (int B : Bs) {
-    const int groups = ZS_KLPQ_THREADS / klpq_group_lanes(K);
+    const int groups = ZS_KLPQ_THREADS / group_lanes(K);
     int blocks = (B + groups - 1) / groups;
     walk_map(K, B, ZS_KLPQ_THREADS, blocks);
     walk_map(K, B, ZS_KLPQ_THREADS, blocks > 1 ? blocks / 2 : 1);          // fewer workgroups than steps: the stride loop
@@ -240,7 +224,7 @@ static void check_mean(int64_t B) {
   for (int64_t b = 0; b < B; ++b) { costs[b] = (T)(10.0 * normal01() + 30.0); sum += costs[b]; asum += fabsl((ld)costs[b]); }
   T v[ZS_KLPQ_WAVE];
   for (int l = 0; l < ZS_KLPQ_WAVE; ++l) v[l] = klpq_mean_lane<T>(costs, B, l);
-  klpq_butterfly_host(v, ZS_KLPQ_WAVE, [](T a, T x) { return a + x; });
+  group_butterfly_host(v, ZS_KLPQ_WAVE, [](T a, T x) { return a + x; });
   const T mean = v[0] / (T)B;
   expect(fabsl((ld)mean - sum / B) <= ((B + 63) / 64 + 8) * u * asum / B, "batch mean against long double", (double)mean, (double)(sum / B));
   free(costs);
@@ -254,10 +238,5 @@ int main() {
   for (int B : Bs) { check_mean<float>(B); check_mean<double>(B); }
   check_mean<float>(ZS_KLPQ_MEAN_MAX_B);
   check_mean<double>(ZS_KLPQ_MEAN_MAX_B);
-  if (n_fail) {
-    fprintf(stderr, "%d of %ld checks failed\n", n_fail, n_checks);
-    return 1;
-  }
-  printf("klpq host math ok: %ld checks\n", n_checks);
-  return 0;
+  return finish("klpq host math ok");
 }

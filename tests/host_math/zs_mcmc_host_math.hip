@@ -11,17 +11,8 @@
 #include <vector>
 
 #include "../../zhusuan-pytorch_amd/csrc/zs_mcmc_math.h"
+#include "zs_host_check.h"
 
-static long n_checks = 0;
-static int n_fail = 0;
-static void expect(bool ok, const char* what, double got, double want) {
-  ++n_checks;
-  if (!ok) {
-    if (n_fail < 20) fprintf(stderr, "FAIL %s: got %.17g want %.17g\n", what, got, want);
-    ++n_fail;
-  }
-}
-typedef long double ld;
 template <typename T> static ld rel_bound() { return sizeof(T) == 4 ? ldexpl(1.0L, -20) : ldexpl(1.0L, -48); }
 template <typename T>
 static void near(T got, ld want, ld S, const char* what) {
@@ -157,10 +148,5 @@ int main() {
     walk_layout(l, 3);                       // a small grid: the grid-stride loop runs many rounds
     walk_layout(l, 256 * 1024);              // the kernel's largest grid: one round and, for the last layout, a second one with the tail
   }
-  if (n_fail) {
-    fprintf(stderr, "%d of %ld checks FAILED\n", n_fail, n_checks);
-    return 1;
-  }
-  printf("mcmc host math ok: %ld checks\n", n_checks);
-  return 0;
+  return finish("mcmc host math ok");
 }

@@ -1,4 +1,4 @@
-// The arithmetic and the lane map of the multivariate-normal kernels (csrc/zs_mvn_math.h with zs_flat_math.h: __host__ __device__)
+// The arithmetic and the lane map of the multivariate-normal kernels (csrc/zs_mvn_math.h with zs_group_math.h: __host__ __device__)
 // compiled for the HOST and run under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_mvn_host_math.py):
 //     hipcc -x hip --cuda-host-only -Xarch_host -fsanitize=address,undefined ...
 // (1) the matvec and the two substitutions in the kernels' own order (mvn_matvec_row, mvn_forward_row, mvn_backward_row: the
@@ -14,25 +14,9 @@
 #include <vector>
 
 #include "../../zhusuan-pytorch_amd/csrc/zs_mvn_math.h"
+#include "zs_host_check.h"
 
-static long n_checks = 0;
-static int n_fail = 0;
-static void expect(bool ok, const char* what, double got, double want) {
-  ++n_checks;
-  if (!ok) {
-    if (n_fail < 20) fprintf(stderr, "FAIL %s: got %.17g want %.17g\n", what, got, want);
-    ++n_fail;
-  }
-}
-typedef long double ld;
 template <typename T> static ld unit() { return sizeof(T) == 4 ? ldexpl(1.0L, -24) : ldexpl(1.0L, -53); }
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static double uniform01() {          // xorshift64*: strictly inside (0, 1)
-  rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
-  return ((double)((rng_state * 0x2545F4914F6CDD1Dull) >> 11) + 0.5) * ldexp(1.0, -53);
-}
-static double normal01() { return sqrt(-2.0 * log(uniform01())) * cos(6.283185307179586 * uniform01()); }
 
 static const int Ds[] = {1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 31, 32, 33, 63, 64};
 
@@ -143,9 +127,9 @@ static void check_arithmetic() {
 // ---------------------------------------------------------------- (2)
 static void check_lane_groups() {
   const int64_t Rs[] = {1, 3, 65};
-  expect(zs::mvn_group_lanes(0) == 1 && zs::mvn_group_lanes(65) == 64, "group lanes at the edges", 0, 0);
+  expect(zs::group_lanes(0) == 1 && zs::group_lanes(65) == 64, "group lanes at the edges", 0, 0);
   for (int D : Ds) {
-    const int G = zs::mvn_group_lanes(D);
+    const int G = zs::group_lanes(D);
     expect(G >= D && (G == 1 || G / 2 < D) && (G & (G - 1)) == 0 && G <= 64, "group lanes", G, D);
     // the wave's tile: every (group, i >= j) has its own place inside it
     std::vector<unsigned char> tile((size_t)zs::mvn_tile_elements(G), 0);          // .at() checks the bound
@@ -159,14 +143,14 @@ static void check_lane_groups() {
       unsigned char* touched = (unsigned char*)calloc((size_t)(R * D * D), 1);      // (row, i, j) of the walk
       unsigned char* lower = (unsigned char*)calloc((size_t)(R * D * D), 1);        // (row, i >= j) read on the way in
       for (int b = 0; b < blocks; ++b) for (int tid = 0; tid < ZS_MVN_THREADS; ++tid) {
-        const zs::MvnPlace pl = zs::mvn_place(tid, G);
-        expect(pl.i >= 0 && pl.i < G && pl.first % G == 0 && pl.first + G <= 64 && tid - pl.first == pl.i && pl.grp == pl.first / G &&
-               pl.groups * G == 64, "a group stays inside its wave", pl.first, pl.i);
-        for (int64_t rb = zs::mvn_row_first(b, pl); rb < R; rb += zs::mvn_row_step(blocks, pl)) {
+        const zs::GroupPlace pl = zs::group_place(tid, ZS_MVN_THREADS, G);
+        expect(pl.lane >= 0 && pl.lane < G && pl.first % G == 0 && pl.first + G <= 64 && tid - pl.first == pl.lane && pl.grp == pl.first / G &&
+               pl.groups * G == 64, "a group stays inside its wave", pl.first, pl.lane);
+        for (int64_t rb = zs::group_row_first(b, pl); rb < R; rb += zs::group_row_step(blocks, pl)) {
           const int64_t r = rb + pl.grp;
           if (r >= R) continue;
-          if (pl.i < D) ++owned[r * D + pl.i];
-          for (zs::MvnWalk w = zs::mvn_walk_first(pl.i, D); w.i < D; zs::mvn_walk_next(w, G, D)) {
+          if (pl.lane < D) ++owned[r * D + pl.lane];
+          for (zs::MvnWalk w = zs::mvn_walk_first(pl.lane, D); w.i < D; zs::mvn_walk_next(w, G, D)) {
             expect(w.j >= 0 && w.j < D, "the walk stays inside a row", w.j, D);
             ++touched[(r * D + w.i) * D + w.j];
             if (w.j <= w.i) ++lower[(r * D + w.i) * D + w.j];
@@ -192,10 +176,5 @@ int main() {
   check_arithmetic<float>();
   check_arithmetic<double>();
   check_lane_groups();
-  if (n_fail) {
-    fprintf(stderr, "%d of %ld checks failed\n", n_fail, n_checks);
-    return 1;
-  }
-  printf("mvn host math ok: %ld checks\n", n_checks);
-  return 0;
+  return finish("mvn host math ok");
 }

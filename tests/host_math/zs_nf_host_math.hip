@@ -1,4 +1,4 @@
-// The arithmetic and the lane map of the planar / Householder flow kernels (csrc/zs_nf_math.h with zs_flat_math.h: __host__
+// The arithmetic and the lane map of the planar / Householder flow kernels (csrc/zs_nf_math.h with zs_group_math.h: __host__
 // __device__) compiled for the HOST and run under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_nf_host_math.py):
 //     hipcc -x hip --cuda-host-only -Xarch_host -fsanitize=address,undefined ...
 // (1) the parameter formulas (s in {-30, -3, 0, 3, 30}), one planar layer with its backward pieces and the parameter chain
@@ -14,29 +14,13 @@
 #include <vector>
 
 #include "../../zhusuan-pytorch_amd/csrc/zs_nf_math.h"
+#include "zs_host_check.h"
 
-static long n_checks = 0;
-static int n_fail = 0;
-static void expect(bool ok, const char* what, double got, double want) {
-  ++n_checks;
-  if (!ok) {
-    if (n_fail < 20) fprintf(stderr, "FAIL %s: got %.17g want %.17g\n", what, got, want);
-    ++n_fail;
-  }
-}
-typedef long double ld;
 // 2^-20 (2^-48) of the summed term magnitudes: the unit of a result through a library function (tests/README_nf.md)
 template <typename T> static ld lib_unit() { return sizeof(T) == 4 ? ldexpl(1.0L, -20) : ldexpl(1.0L, -48); }
 template <typename T> static void close(const char* what, T got, ld want, ld mag, int D) {
   expect(isfinite((double)got) && fabsl((ld)got - want) <= (D + 8) * lib_unit<T>() * mag, what, (double)got, (double)want);
 }
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-static double uniform01() {          // xorshift64*: strictly inside (0, 1)
-  rng_state ^= rng_state >> 12; rng_state ^= rng_state << 25; rng_state ^= rng_state >> 27;
-  return ((double)((rng_state * 0x2545F4914F6CDD1Dull) >> 11) + 0.5) * ldexp(1.0, -53);
-}
-static double normal01() { return sqrt(-2.0 * log(uniform01())) * cos(6.283185307179586 * uniform01()); }
 
 static const int Ds[] = {1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 31, 32, 33, 40, 63, 64};
 
@@ -156,11 +140,11 @@ static void check_arithmetic() {
 static void check_maps() {
   const int64_t Rs[] = {1, 3, 65};
   const int Ls[] = {1, 32};
-  expect(zs::nf_group_lanes(0) == 1 && zs::nf_group_lanes(65) == 64, "group lanes at the edges", 0, 0);
+  expect(zs::group_lanes(0) == 1 && zs::group_lanes(65) == 64, "group lanes at the edges", 0, 0);
   expect(zs::nf_workgroups(1, 64) == 1 && zs::nf_workgroups(65, 64) == 65 && zs::nf_workgroups(65, 4) == 5 &&
          zs::nf_workgroups((int64_t)1 << 40, 1) == ZS_NF_MAX_WORKGROUPS, "workgroups", 0, 0);
   for (int D : Ds) {
-    const int G = zs::nf_group_lanes(D);
+    const int G = zs::group_lanes(D);
     expect(G >= D && (G == 1 || G / 2 < D) && (G & (G - 1)) == 0 && G <= 64, "group lanes", G, D);
     for (int64_t R : Rs) for (int L : Ls) {
       const int own = zs::nf_workgroups(R, G);
@@ -171,23 +155,23 @@ static void check_maps() {
         const int64_t n_lds = zs::nf_planar_bwd_lds(D, L, G), z_at = n_lds - zs::nf_householder_bwd_lds(L), t_at = (int64_t)L * D + L;
         for (int b = 0; b < blocks; ++b) {
           bool first_tile = true;
-          const zs::NfPlace p0 = zs::nf_place(0, G);
-          for (int64_t rb = zs::nf_row_first(b, p0); rb < R; rb += zs::nf_row_step(blocks, p0), first_tile = false) {
+          const zs::GroupPlace p0 = zs::group_place(0, ZS_NF_THREADS, G);
+          for (int64_t rb = zs::group_row_first(b, p0); rb < R; rb += zs::group_row_step(blocks, p0), first_tile = false) {
             unsigned char* lds = (unsigned char*)calloc((size_t)n_lds, 1);          // one tile's writes
             for (int tid = 0; tid < ZS_NF_THREADS; ++tid) {
-              const zs::NfPlace pl = zs::nf_place(tid, G);
-              expect(pl.i >= 0 && pl.i < G && pl.first % G == 0 && pl.first + G <= 64 && tid - pl.first == pl.i && pl.grp == pl.first / G &&
-                     pl.groups * G == 64, "a group stays inside its wave", pl.first, pl.i);
+              const zs::GroupPlace pl = zs::group_place(tid, ZS_NF_THREADS, G);
+              expect(pl.lane >= 0 && pl.lane < G && pl.first % G == 0 && pl.first + G <= 64 && tid - pl.first == pl.lane && pl.grp == pl.first / G &&
+                     pl.groups * G == 64, "a group stays inside its wave", pl.first, pl.lane);
               const int64_t r = rb + pl.grp;
               for (int l = 0; l < L; ++l) {
                 ++lds[z_at + zs::nf_z_index(l, tid)];
-                if (pl.i == 0) ++lds[t_at + zs::nf_t_index(l, pl.grp, pl.groups)];
-                if (pl.i < D && tid < D) ++lds[(int64_t)l * D + tid];          // uh_l[d] by lane d of the wave
+                if (pl.lane == 0) ++lds[t_at + zs::nf_t_index(l, pl.grp, pl.groups)];
+                if (pl.lane < D && tid < D) ++lds[(int64_t)l * D + tid];          // uh_l[d] by lane d of the wave
                 if (tid == 0) ++lds[(int64_t)L * D + l];                        // c_l
-                if (r < R && pl.i < D) ++owned[(r * D + pl.i) * L + l];
+                if (r < R && pl.lane < D) ++owned[(r * D + pl.lane) * L + l];
                 if (first_tile) {
                   const int64_t P = zs::nf_partial_row(b, l, D, L);
-                  if (pl.grp == 0 && pl.i < D) { ++part[P + zs::nf_partial_guh(pl.i)]; ++part[P + zs::nf_partial_gw(pl.i, D)]; }
+                  if (pl.grp == 0 && pl.lane < D) { ++part[P + zs::nf_partial_guh(pl.lane)]; ++part[P + zs::nf_partial_gw(pl.lane, D)]; }
                   if (tid == 0) { ++part[P + zs::nf_partial_gb(D)]; ++part[P + zs::nf_partial_gc(D)]; }
                 }
               }
@@ -214,10 +198,5 @@ int main() {
   check_arithmetic<float>();
   check_arithmetic<double>();
   check_maps();
-  if (n_fail) {
-    fprintf(stderr, "%d of %ld checks failed\n", n_fail, n_checks);
-    return 1;
-  }
-  printf("nf host math ok: %ld checks\n", n_checks);
-  return 0;
+  return finish("nf host math ok");
 }

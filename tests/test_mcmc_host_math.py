@@ -4,21 +4,8 @@ main, is built for the host with the sanitizers and run directly -- nothing is p
 holds every kind's arithmetic to long-double restatements over a grid of operands (a = 0, g = 0, hyper-parameters at their
 extremes; the bound of tests/test_mcmc_kernel.py) and walks the element form's indexing (bisection, clamping, tail) over
 exactly-sized heap arrays for that test's layouts."""
-import os
-import shutil
-import subprocess
-
-from conftest import ROOT
+from host_math_runner import run_host_math
 
 
 def test_sampler_arithmetic_and_indexing_on_the_host_under_asan_and_ubsan(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "zs_mcmc_host_math")
-    src = os.path.join(ROOT, "tests", "host_math", "zs_mcmc_host_math.hip")
-    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                        "-Xarch_host", "-fno-sanitize-recover=all", src, "-o", exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "mcmc host math ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
-    assert int(r.stdout.split("ok:")[1].split()[0]) > 100000
+    run_host_math(tmp_path, "zs_mcmc_host_math.hip", "mcmc host math ok", 100000)

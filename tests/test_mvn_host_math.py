@@ -1,26 +1,13 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer on the CPU for the multivariate-normal kernels (GPU sanitizers are not available
-on this pool): csrc/zs_mvn_math.h (with zs_flat_math.h) is __host__ __device__; tests/host_math/zs_mvn_host_math.hip, a
+on this pool): csrc/zs_mvn_math.h (with zs_group_math.h) is __host__ __device__; tests/host_math/zs_mvn_host_math.hip, a
 stand-alone program with its own main, is built for the host with the sanitizers and run directly -- nothing is preloaded,
 nothing is loaded into python.  It runs the matvec, the two substitutions and the density in the kernels' own order against long
 double for every D of tests/test_mvn_kernel.py, to that test's bounds, and walks the lane-group map, the walk of a group over a
 row's matrix and the LDS tile places over exactly-sized heap arrays for every D and R in {1, 3, 65}: every (row, i) and every
 (row, i >= j) is owned exactly once, nothing above the diagonal is read, and a group never crosses its wave."""
-import os
-import shutil
-import subprocess
-
-from conftest import ROOT
+from host_math_runner import run_host_math
 
 
 def test_mvn_arithmetic_and_lane_group_maps_on_the_host_under_asan_and_ubsan(tmp_path):
     import zhusuan.distributions.multivariate  # noqa: F401  (the feature under test)
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    exe = str(tmp_path / "zs_mvn_host_math")
-    src = os.path.join(ROOT, "tests", "host_math", "zs_mvn_host_math.hip")
-    r = subprocess.run([hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-Xarch_host", "-fsanitize=address,undefined",
-                        "-Xarch_host", "-fno-sanitize-recover=all", src, "-o", exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "mvn host math ok" in r.stdout, (r.stdout + r.stderr)[-3000:]
-    assert int(r.stdout.split("ok:")[1].split()[0]) > 20000
+    run_host_math(tmp_path, "zs_mvn_host_math.hip", "mvn host math ok", 20000)

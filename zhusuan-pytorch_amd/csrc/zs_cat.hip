@@ -62,11 +62,6 @@ __device__ __forceinline__ void uniform4(int64_t i0, const PhiloxCall& pc, T out
   }
 }
 
-template <typename T>
-__device__ __forceinline__ T group_sum(T v, int G) {
-  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);
-  return v;
-}
 // the merged pair of the group, the same bits in all of its lanes (`first`: the group's first lane within the wave)
 template <typename T>
 __device__ __forceinline__ CatMS<T> group_ms(CatMS<T> a, int G, int first) {
@@ -89,16 +84,17 @@ __global__ __launch_bounds__(THREADS) void k_cat_sample(const T* __restrict__ lo
                                                         const uint64_t* __restrict__ rs) {
   if (rs) { seed = rs[0]; call += rs[1]; }
   const PhiloxCall pc = philox_call(call, seed);
-  const CatPlace pl = cat_place((int)blockIdx.x, (int)threadIdx.x, (int)gridDim.x, G);
-  const int64_t step = cat_chunk_step(G);
-  for (int64_t it = pl.item; it < items; it += pl.stride) {
+  const int block = (int)blockIdx.x, blocks = (int)gridDim.x;
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  const int64_t item0 = cat_item_first(block, pl), stride = cat_item_step(blocks, pl), step = cat_chunk_step(G);
+  for (int64_t it = item0; it < items; it += stride) {
     const int64_t r = mod_fast(it, R);
     const T* lrow = logits + r * N;
     const int64_t base = it * N;
     CatMS<T> ms = cat_ms_empty<T>();
     T bv = cat_neg_inf<T>();
     int32_t bj = INT32_MAX;
-    for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+    for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
       T l[4], uu[4];
       load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
       if (u) load4<T, VEC>(u + base, j0, N, (T)0.5, uu);
@@ -118,12 +114,12 @@ __global__ __launch_bounds__(THREADS) void k_cat_sample(const T* __restrict__ lo
       if (cat_better(ov, oj, bv, bj)) { bv = ov; bj = oj; }
     }
     ms = group_ms(ms, G, pl.first);
-    if (pl.g == 0) {
+    if (pl.lane == 0) {
       if (idx) idx[it] = (int64_t)bj;
       if (lp) lp[it] = bj < N ? cat_logmass(lrow[bj], cat_lse(ms)) : cat_nan<T>();
     }
     if (onehot) {
-      for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+      for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
         T h[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) h[c] = j0 + c == (int64_t)bj ? (T)1 : (T)0;
@@ -138,15 +134,16 @@ template <typename T, bool VEC>
 __global__ __launch_bounds__(THREADS) void k_cat_logprob(const T* __restrict__ logits, const int64_t* __restrict__ idx,
                                                          const T* __restrict__ x, int64_t prow, T* __restrict__ lp, int64_t items,
                                                          int64_t R, int64_t N, int G) {
-  const CatPlace pl = cat_place((int)blockIdx.x, (int)threadIdx.x, (int)gridDim.x, G);
-  const int64_t step = cat_chunk_step(G);
-  for (int64_t it = pl.item; it < items; it += pl.stride) {
+  const int block = (int)blockIdx.x, blocks = (int)gridDim.x;
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  const int64_t item0 = cat_item_first(block, pl), stride = cat_item_step(blocks, pl), step = cat_chunk_step(G);
+  for (int64_t it = item0; it < items; it += stride) {
     const int64_t r = mod_fast(it, R);
     const int64_t xr = mod_fast(it, prow);
     const T* lrow = logits + r * N;
     CatMS<T> ms = cat_ms_empty<T>();
     T sxl = (T)0, sx = (T)0;
-    for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+    for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
       T l[4];
       load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
       cat_ms_push4(ms, l);
@@ -165,8 +162,8 @@ __global__ __launch_bounds__(THREADS) void k_cat_logprob(const T* __restrict__ l
     if (x) {
       sxl = group_sum(sxl, G);
       sx = group_sum(sx, G);
-      if (pl.g == 0) lp[it] = cat_weight_logmass(sxl, sx, lse);
-    } else if (pl.g == 0) {
+      if (pl.lane == 0) lp[it] = cat_weight_logmass(sxl, sx, lse);
+    } else if (pl.lane == 0) {
       const int64_t j = idx[xr];
       lp[it] = j >= 0 && j < N ? cat_logmass(lrow[j], lse) : cat_nan<T>();
     }
@@ -179,14 +176,15 @@ template <typename T, bool VEC>
 __global__ __launch_bounds__(THREADS) void k_cat_logprob_bwd(const T* __restrict__ logits, const int64_t* __restrict__ idx,
                                                              const T* __restrict__ x, int64_t prow, const T* __restrict__ glp,
                                                              T* glogits, T* __restrict__ gx, int64_t K, int64_t R, int64_t N, int G) {
-  const CatPlace pl = cat_place((int)blockIdx.x, (int)threadIdx.x, (int)gridDim.x, G);
-  const int64_t step = cat_chunk_step(G);
+  const int block = (int)blockIdx.x, blocks = (int)gridDim.x;
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  const int64_t item0 = cat_item_first(block, pl), stride = cat_item_step(blocks, pl), step = cat_chunk_step(G);
   const bool shared = prow == R;          // the value has no particle axis
-  for (int64_t r = pl.item; r < R; r += pl.stride) {
+  for (int64_t r = item0; r < R; r += stride) {
     const T* lrow = logits + r * N;
     CatMS<T> ms = cat_ms_empty<T>();
     T W = (T)0;
-    for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+    for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
       T l[4], A[4] = {(T)0, (T)0, (T)0, (T)0};
       load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
       cat_ms_push4(ms, l);
@@ -213,7 +211,7 @@ __global__ __launch_bounds__(THREADS) void k_cat_logprob_bwd(const T* __restrict
     ms = group_ms(ms, G, pl.first);
     W = group_sum(W, G);
     const T lse = cat_lse(ms);
-    for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+    for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
       T l[4];
       load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
       if (glogits) {
@@ -245,14 +243,15 @@ __global__ __launch_bounds__(THREADS) void k_cat_relaxed_sample(const T* __restr
                                                                 const uint64_t* __restrict__ rs) {
   if (rs) { seed = rs[0]; call += rs[1]; }
   const PhiloxCall pc = philox_call(call, seed);
-  const CatPlace pl = cat_place((int)blockIdx.x, (int)threadIdx.x, (int)gridDim.x, G);
-  const int64_t step = cat_chunk_step(G);
-  for (int64_t it = pl.item; it < items; it += pl.stride) {
+  const int block = (int)blockIdx.x, blocks = (int)gridDim.x;
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  const int64_t item0 = cat_item_first(block, pl), stride = cat_item_step(blocks, pl), step = cat_chunk_step(G);
+  for (int64_t it = item0; it < items; it += stride) {
     const int64_t r = mod_fast(it, R);
     const T* lrow = logits + r * N;
     const int64_t base = it * N;
     CatMS<T> ma = cat_ms_empty<T>();
-    for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+    for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
       T l[4], uu[4], a[4];
       load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
       if (u) load4<T, VEC>(u + base, j0, N, (T)0.5, uu);
@@ -266,7 +265,7 @@ __global__ __launch_bounds__(THREADS) void k_cat_relaxed_sample(const T* __restr
     // second walk over the lane's own chunks (the row is still in the cache; the draw is recomputed, not stored)
     CatMS<T> mt = cat_ms_empty<T>();
     T sum_t = (T)0, sum_y = (T)0;
-    for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+    for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
       T l[4], uu[4], yy[4], t[4];
       load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
       if (u) load4<T, VEC>(u + base, j0, N, (T)0.5, uu);
@@ -291,7 +290,7 @@ __global__ __launch_bounds__(THREADS) void k_cat_relaxed_sample(const T* __restr
       mt = group_ms(mt, G, pl.first);
       sum_t = group_sum(sum_t, G);
       sum_y = group_sum(sum_y, G);
-      if (pl.g == 0) lp[it] = cat_relaxed_lp(c0, sum_t, (T)N, cat_lse(mt), sum_y, exp_space != 0);
+      if (pl.lane == 0) lp[it] = cat_relaxed_lp(c0, sum_t, (T)N, cat_lse(mt), sum_y, exp_space != 0);
     }
   }
 }
@@ -303,11 +302,12 @@ __global__ __launch_bounds__(THREADS) void k_cat_relaxed_bwd(const T* __restrict
                                                              const T* __restrict__ gy, const T* __restrict__ gey,
                                                              const T* __restrict__ glp, T* __restrict__ gy_out, T* glogits,
                                                              int64_t K, int64_t R, int64_t N, int G, T tau, int exp_space) {
-  const CatPlace pl = cat_place((int)blockIdx.x, (int)threadIdx.x, (int)gridDim.x, G);
-  const int64_t step = cat_chunk_step(G);
+  const int block = (int)blockIdx.x, blocks = (int)gridDim.x;
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  const int64_t item0 = cat_item_first(block, pl), stride = cat_item_step(blocks, pl), step = cat_chunk_step(G);
   const T e = exp_space ? (T)1 : (T)0, n = (T)N;
   const bool shared = prow == R;
-  for (int64_t r = pl.item; r < R; r += pl.stride) {
+  for (int64_t r = item0; r < R; r += stride) {
     const T* lrow = logits + r * N;
     for (int64_t k = 0; k < K; ++k) {
       const int64_t it = k * R + r, base = it * N;
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(THREADS) void k_cat_relaxed_bwd(const T* __restrict
       const T gk = glp ? glp[it] : (T)0;
       CatMS<T> mt = cat_ms_empty<T>();
       T sg = (T)0;
-      for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+      for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
         T l[4], yy[4], t[4];
         load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
         load4<T, VEC>(yrow, j0, N, (T)0, yy);
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(THREADS) void k_cat_relaxed_bwd(const T* __restrict
       const T lse_t = cat_lse(mt);
       T S = (T)0;
       if (MODE == 0) S = flat_fma(-gk * e, n, group_sum(sg, G));
-      for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+      for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
         T l[4], yy[4], acc[4] = {(T)0, (T)0, (T)0, (T)0}, go[4];
         load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
         load4<T, VEC>(yrow, j0, N, (T)0, yy);
@@ -369,14 +369,15 @@ template <typename T, bool VEC>
 __global__ __launch_bounds__(THREADS) void k_cat_relaxed_logprob(const T* __restrict__ logits, const T* __restrict__ y, int64_t prow,
                                                                  T* __restrict__ lp, int64_t items, int64_t R, int64_t N, int G, T tau,
                                                                  T c0, int exp_space) {
-  const CatPlace pl = cat_place((int)blockIdx.x, (int)threadIdx.x, (int)gridDim.x, G);
-  const int64_t step = cat_chunk_step(G);
-  for (int64_t it = pl.item; it < items; it += pl.stride) {
+  const int block = (int)blockIdx.x, blocks = (int)gridDim.x;
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  const int64_t item0 = cat_item_first(block, pl), stride = cat_item_step(blocks, pl), step = cat_chunk_step(G);
+  for (int64_t it = item0; it < items; it += stride) {
     const T* lrow = logits + mod_fast(it, R) * N;
     const T* yrow = y + mod_fast(it, prow) * N;
     CatMS<T> mt = cat_ms_empty<T>();
     T sum_t = (T)0, sum_y = (T)0;
-    for (int64_t j0 = cat_chunk_first(pl.g); j0 < N; j0 += step) {
+    for (int64_t j0 = cat_chunk_first(pl.lane); j0 < N; j0 += step) {
       T l[4], yy[4], t[4];
       load4<T, VEC>(lrow, j0, N, cat_neg_inf<T>(), l);
       load4<T, VEC>(yrow, j0, N, (T)0, yy);
@@ -392,7 +393,7 @@ __global__ __launch_bounds__(THREADS) void k_cat_relaxed_logprob(const T* __rest
     mt = group_ms(mt, G, pl.first);
     sum_t = group_sum(sum_t, G);
     sum_y = group_sum(sum_y, G);
-    if (pl.g == 0) lp[it] = cat_relaxed_lp(c0, sum_t, (T)N, cat_lse(mt), sum_y, exp_space != 0);
+    if (pl.lane == 0) lp[it] = cat_relaxed_lp(c0, sum_t, (T)N, cat_lse(mt), sum_y, exp_space != 0);
   }
 }
 

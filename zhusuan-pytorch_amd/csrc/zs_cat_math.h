@@ -1,12 +1,13 @@
 // The arithmetic of the categorical kernels (include/zs_cat.h, zs_cat.hip): the Gumbel transform, the running (max, sum-exp)
-// pair of a row and its merge, the lane-group map of a row and the density formulas.  __host__ __device__, so that
-// tests/host_math/zs_cat_host_math.hip runs the same code on the host under the sanitizers.
+// pair of a row and its merge, what a row adds to the lane-group map of zs_group_math.h (chunks of four, work items) and the
+// density formulas.  __host__ __device__, so that tests/host_math/zs_cat_host_math.hip runs the same code on the host under the
+// sanitizers.
 //
 // Logarithms and exponentials are the accurate library ones (logf / expf, log / exp): the winner of a Gumbel-max draw is the
 // element with u closest to 1, where -log u is tiny and a base-2 hardware logarithm loses the relative accuracy the draw needs.
 #pragma once
 #include <math.h>
-#include "zs_flat_math.h"
+#include "zs_group_math.h"
 
 // a * b + c rounds once only where flat_fma says so: the aligned and the element path must agree bit for bit
 #pragma clang fp contract(off)
@@ -24,39 +25,21 @@ ZS_HD T cat_nan() { return (T)NAN; }
 
 // ---------------------------------------------------------------- lane groups
 // A row of N categories is cut into chunks of four consecutive categories (one 16-byte access).  A group of
-// G = min(64, next_pow2(ceil(N / 4))) consecutive lanes owns a row: lane g of the group owns the chunks g, g + G, g + 2G, ...
+// G = group_lanes(ceil(N / 4)) consecutive lanes owns a row: lane g = pl.lane of the group owns the chunks g, g + G, g + 2G, ...
 // So N <= 4 takes one lane per row (64 rows per wave), N <= 256 one chunk per lane, and a wider row is strided over by a whole
 // wave; a row never leaves its wave.
-ZS_HD int cat_group_lanes(int64_t N) {
-  const int64_t chunks = (N + 3) >> 2;
-  int g = 1;
-  while (g < 64 && g < chunks) g <<= 1;
-  return g;
-}
+ZS_HD int cat_group_lanes(int64_t N) { return group_lanes((N + 3) >> 2); }
 // The walk of lane g over its chunks, as every kernel writes it:
 //   for (int64_t j0 = cat_chunk_first(g); j0 < N; j0 += cat_chunk_step(G))   -- j0: the first category of a chunk
 ZS_HD int64_t cat_chunk_first(int g) { return (int64_t)g << 2; }
 ZS_HD int64_t cat_chunk_step(int G) { return (int64_t)G << 2; }
 
-// The place of a thread in the grid, as every kernel takes it from (blockIdx.x, threadIdx.x, gridDim.x): workgroups of
-// CAT_THREADS threads hold CAT_THREADS / G lane groups, the groups of the grid stride over the work items (rows or particle-rows):
-//   for (int64_t it = p.item; it < items; it += p.stride)
+// Workgroups of ZS_CAT_THREADS threads hold ZS_CAT_THREADS / G lane groups (the place is zs_group_math.h's); the groups of the
+// grid stride over the work items (rows or particle-rows), and each group leaves the loop on its own:
+//   item0 = cat_item_first(block, pl), stride = cat_item_step(blocks, pl);   for (int64_t it = item0; it < items; it += stride)
 #define ZS_CAT_THREADS 256
-struct CatPlace {
-  int g;            // lane within the group
-  int first;        // the group's first lane within its wave of 64
-  int64_t item;     // first work item of the group
-  int64_t stride;   // groups in the grid
-};
-ZS_HD CatPlace cat_place(int block, int thread, int blocks, int G) {
-  CatPlace p;
-  const int per_block = ZS_CAT_THREADS / G;
-  p.g = thread & (G - 1);
-  p.first = (thread & 63) & ~(G - 1);
-  p.item = (int64_t)block * per_block + thread / G;
-  p.stride = (int64_t)blocks * per_block;
-  return p;
-}
+ZS_HD int64_t cat_item_first(int block, const GroupPlace& p) { return group_row_first(block, p) + p.grp; }
+ZS_HD int64_t cat_item_step(int blocks, const GroupPlace& p) { return group_row_step(blocks, p); }
 
 // ---------------------------------------------------------------- the Gumbel transform
 // v = l - log(-log u): u lies strictly inside (0, 1), so both logarithms are finite

@@ -1,6 +1,6 @@
-// What the satellite libraries (zs_mcmc.hip, zs_hmc.hip, zs_flow.hip, zs_cat.hip) share: the explicit fma, the index maps of a flat index
-// space over a table of tensors, and the 16-byte group of four.  __host__ __device__, so that the host-side sanitizer tests
-// (tests/host_math/) run the same code.
+// What all seven satellite libraries share (zs_mcmc.hip and zs_hmc.hip directly; zs_flow.hip, zs_cat.hip, zs_mvn.hip, zs_klpq.hip
+// and zs_nf.hip through zs_group_math.h): the explicit fma, the index maps of a flat index space over a table of tensors, and
+// the 16-byte group of four.  __host__ __device__, so that the host-side sanitizer tests (tests/host_math/) run the same code.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "zs_flow_math.h"
-#include "zs_flat_math.h"          // Vec4
+#include "zs_group_math.h"         // group_sum; Vec4 (zs_flat_math.h)
 #include "../../include/zs_hip.h"
 #include "../../include/zs_flow.h"
 
@@ -270,13 +270,6 @@ __global__ __launch_bounds__(kBlock) void k_made_inv_col(const T* __restrict__ u
 }
 
 // ---------------------------------------------------------------------------------------------- FlowDistribution tail
-template <typename T>
-__device__ __forceinline__ T wave_sum_fixed(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one wavefront per row, kBlock / 64 rows per workgroup
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_tail(int base, const T* __restrict__ z, const T* __restrict__ loc,
@@ -290,7 +283,7 @@ __global__ __launch_bounds__(kBlock) void k_tail(int base, const T* __restrict__
       const int64_t i = flow_at(b, d, D), ip = param_rows ? i : d;
       acc = flow_add(acc, flow_base_lp(base, z[i], loc[ip], scale[ip]));
     }
-    acc = wave_sum_fixed(acc);
+    acc = group_sum(acc, ZS_WAVE);
     if (lane == 0) {
       if (logdet_kind == ZS_FLOW_LOGDET_SCALAR) acc += logdet[0];
       else if (logdet_kind == ZS_FLOW_LOGDET_ROWS) acc += logdet[b];

@@ -18,17 +18,6 @@ using namespace zs;
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ T group_sum(T v, int G) {
-  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);
-  return v;
-}
-template <typename T>
-__device__ __forceinline__ T group_max(T v, int G) {
-  for (int o = G >> 1; o > 0; o >>= 1) v = klpq_max(v, __shfl_xor(v, o, ZS_WAVE));
-  return v;
-}
-
 // ---------------------------------------------------------------- Q1
 // gridDim.x workgroups of blockDim.x threads, blockDim.x / G datapoints each per step.  With mean_cost the launch is one workgroup.
 template <typename T>
@@ -38,21 +27,21 @@ __global__ __launch_bounds__(ZS_KLPQ_MEAN_THREADS) void k_klpq_forward(const Klp
                                                                        T* __restrict__ mean_cost) {
   __shared__ T costs[ZS_KLPQ_MEAN_MAX_B];
   const bool model_grad = (flags & ZS_KLPQ_MODEL_GRAD) != 0, bound_only = (flags & ZS_KLPQ_BOUND_ONLY) != 0;
-  const KlpqPlace pl = klpq_place((int)threadIdx.x, (int)blockDim.x, G);
-  for (int64_t rb = klpq_row_first((int)blockIdx.x, pl); rb < B; rb += klpq_row_step((int)gridDim.x, pl)) {
+  const GroupPlace pl = group_place((int)threadIdx.x, (int)blockDim.x, G);
+  for (int64_t rb = group_row_first((int)blockIdx.x, pl); rb < B; rb += group_row_step((int)gridDim.x, pl)) {
     const int64_t b = rb + pl.grp;
     const bool valid = b < B;
     const int64_t Kv = valid ? K : 0;          // a group past the last datapoint walks no particle
     KlpqParticle<T> first = {(T)0, (T)0, (T)0};
-    if (pl.j < Kv) first = klpq_particle<T>(p, q, pl.j, b);
-    const T m = group_max(klpq_lane_max<T>(p, q, b, pl.j, G, Kv, first), G);
-    const T s = group_sum(klpq_lane_sumexp<T>(p, q, b, pl.j, G, Kv, first, m), G);
-    if (bound && valid && pl.j == 0) bound[b] = klpq_bound(m, s, logK);
+    if (pl.lane < Kv) first = klpq_particle<T>(p, q, pl.lane, b);
+    const T m = group_max(klpq_lane_max<T>(p, q, b, pl.lane, G, Kv, first), G);
+    const T s = group_sum(klpq_lane_sumexp<T>(p, q, b, pl.lane, G, Kv, first, m), G);
+    if (bound && valid && pl.lane == 0) bound[b] = klpq_bound(m, s, logK);
     if (bound_only) continue;
-    const KlpqSums<T> part = klpq_lane_weights<T>(p, q, b, pl.j, G, Kv, first, m, s, model_grad, (w && valid) ? w + b * K : nullptr);
+    const KlpqSums<T> part = klpq_lane_weights<T>(p, q, b, pl.lane, G, Kv, first, m, s, model_grad, (w && valid) ? w + b * K : nullptr);
     const T c = -group_sum(part.cost, G);
     const T sq = group_sum(part.sq, G);
-    if (valid && pl.j == 0) {
+    if (valid && pl.lane == 0) {
       if (cost) cost[b] = c;
       if (ess) ess[b] = (T)1 / sq;
       if (mean_cost) costs[b] = c;             // (one workgroup, B <= ZS_KLPQ_MEAN_MAX_B: checked on the host)
@@ -110,7 +99,7 @@ int klpq_forward(const zs_klpq_term* pt, int Tp, const zs_klpq_term* qt, int Tq,
   if (bound_only) w = cost = ess = mean_cost = nullptr;
   if (mean_cost && B > ZS_KLPQ_MEAN_MAX_B) return ZS_ENOTSUP;
   if (K == 0 || B == 0) return 0;
-  const int G = klpq_group_lanes(K);
+  const int G = group_lanes(K);
   const unsigned threads = mean_cost ? ZS_KLPQ_MEAN_THREADS : ZS_KLPQ_THREADS;
   const unsigned grid = mean_cost ? 1u : grid_for(B, (int)threads / G, 256u * 16u);
   hipLaunchKernelGGL((k_klpq_forward<T>), dim3(grid), dim3(threads), 0, (hipStream_t)stream, p, q, K, B, G, flags,
@@ -142,7 +131,7 @@ int klpq_backward(const zs_klpq_term* pt, int Tp, const zs_klpq_term* qt, int Tq
 extern "C" int zs_klpq_abi_version(void) { return ZS_KLPQ_ABI_VERSION; }
 extern "C" int zs_klpq_max_terms(void) { return ZS_KLPQ_MAX_TERMS; }
 extern "C" int64_t zs_klpq_mean_max_batch(void) { return ZS_KLPQ_MEAN_MAX_B; }
-extern "C" int zs_klpq_group_lanes(int64_t K) { return K < 1 ? 0 : klpq_group_lanes(K); }
+extern "C" int zs_klpq_group_lanes(int64_t K) { return K < 1 ? 0 : group_lanes(K); }
 
 #define ZS_KLPQ_ENTRY(SFX, T)                                                                                                       \
   extern "C" int zs_klpq_forward##SFX(const struct zs_klpq_term* p, int Tp, const struct zs_klpq_term* q, int Tq, int64_t K,        \

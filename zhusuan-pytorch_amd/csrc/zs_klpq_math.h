@@ -1,11 +1,11 @@
-// The arithmetic and the lane map of the inclusive-KL kernels (include/zs_klpq.h, zs_klpq.hip): the stride addressing of a term,
-// the left-to-right sums of the two sides, the lane group of a datapoint with each lane's partial of the four k-reductions, the
-// first wave's partial of the batch mean, and the whole per-thread body of the backward.  __host__ __device__, so that
-// tests/host_math/zs_klpq_host_math.hip walks the same code on the host under the sanitizers (a table of host pointers works
-// there like a table of device pointers does in a kernel).
+// The arithmetic of the inclusive-KL kernels (include/zs_klpq.h, zs_klpq.hip): the stride addressing of a term, the
+// left-to-right sums of the two sides, each lane's partial of the four k-reductions of a datapoint (its lane group is
+// zs_group_math.h's), the first wave's partial of the batch mean, and the whole per-thread body of the backward.  __host__
+// __device__, so that tests/host_math/zs_klpq_host_math.hip walks the same code on the host under the sanitizers (a table of host
+// pointers works there like a table of device pointers does in a kernel).
 #pragma once
 #include <math.h>
-#include "zs_flat_math.h"
+#include "zs_group_math.h"
 #include "../../include/zs_klpq.h"
 
 // a * b + c stays two roundings: the same bits whatever the compiler would like to fuse
@@ -22,8 +22,6 @@ ZS_HD float klpq_exp(float x) { return expf(x); }
 ZS_HD double klpq_exp(double x) { return exp(x); }
 ZS_HD float klpq_log(float x) { return logf(x); }
 ZS_HD double klpq_log(double x) { return log(x); }
-ZS_HD float klpq_max(float a, float b) { return fmaxf(a, b); }
-ZS_HD double klpq_max(double a, double b) { return fmax(a, b); }
 
 // ---------------------------------------------------------------- terms
 // One side of the objective as the kernels receive it (by value): the first n rows of the caller's table.
@@ -51,36 +49,13 @@ ZS_HD KlpqParticle<T> klpq_particle(const KlpqSide& p, const KlpqSide& q, int64_
   return v;
 }
 
-// ---------------------------------------------------------------- lane groups
-// A group of G = next_pow2(min(K, 64)) consecutive lanes of one wave owns a datapoint; lane j of the group walks the particles
-// j, j + G, j + 2 G, ... (one particle per lane up to K = 64).  A workgroup of `threads` holds threads / G datapoints.
-ZS_HD int klpq_group_lanes(int64_t K) {
-  int g = 1;
-  while (g < ZS_KLPQ_WAVE && g < K) g <<= 1;
-  return g;
-}
-struct KlpqPlace {
-  int j;            // lane within the group = its first particle (idle when j >= K)
-  int grp;          // the group within the workgroup
-  int groups;       // groups per workgroup = datapoints per step
-};
-ZS_HD KlpqPlace klpq_place(int thread, int threads, int G) {
-  KlpqPlace p;
-  p.j = thread & (G - 1);
-  p.grp = thread / G;
-  p.groups = threads / G;
-  return p;
-}
-// The datapoints of a workgroup -- the trip count is the same for every lane of it, a group past the last datapoint idles
-// through the exchanges (it walks K = 0 particles) and stores nothing:
-//   for (int64_t rb = klpq_row_first(block, pl); rb < B; rb += klpq_row_step(blocks, pl)) { b = rb + pl.grp; valid = b < B; ... }
-ZS_HD int64_t klpq_row_first(int block, const KlpqPlace& p) { return (int64_t)block * p.groups; }
-ZS_HD int64_t klpq_row_step(int blocks, const KlpqPlace& p) { return (int64_t)blocks * p.groups; }
-
 // ---------------------------------------------------------------- a lane's partials of the k-reductions
-// Each walks k = j, j + G, ... < K in ascending order; `first` is particle j, read once by the caller and kept in registers (for
-// K <= 64 it is all a lane has).  The group's value is the xor butterfly over the G partials: klpq_butterfly_* below on the
-// host, shuffles in the kernel.  Neutral partials (-inf, 0) come from lanes without a particle.
+// A group of G = group_lanes(K) consecutive lanes of one wave owns a datapoint (the row of zs_group_math.h); lane pl.lane = j of
+// the group walks the particles j, j + G, j + 2 G, ... (one particle per lane up to K = 64; idle when j >= K).  A workgroup of
+// blockDim.x threads holds blockDim.x / G datapoints; a group past the last datapoint walks K = 0 particles.
+// Each partial walks k = j, j + G, ... < K in ascending order; `first` is particle j, read once by the caller and kept in registers (for
+// K <= 64 it is all a lane has).  The group's value is the xor butterfly over the G partials: group_butterfly_host on the host,
+// shuffles in the kernel (zs_group_math.h).  Neutral partials (-inf, 0) come from lanes without a particle.
 template <typename T>
 ZS_HD KlpqParticle<T> klpq_at(const KlpqSide& p, const KlpqSide& q, int64_t k, int64_t b, int j, const KlpqParticle<T>& first) {
   return k == j ? first : klpq_particle<T>(p, q, k, b);
@@ -88,7 +63,7 @@ ZS_HD KlpqParticle<T> klpq_at(const KlpqSide& p, const KlpqSide& q, int64_t k, i
 template <typename T>
 ZS_HD T klpq_lane_max(const KlpqSide& p, const KlpqSide& q, int64_t b, int j, int G, int64_t K, const KlpqParticle<T>& first) {
   T m = (T)-INFINITY;
-  for (int64_t k = j; k < K; k += G) m = klpq_max(m, klpq_at<T>(p, q, k, b, j, first).lw);
+  for (int64_t k = j; k < K; k += G) m = group_fmax(m, klpq_at<T>(p, q, k, b, j, first).lw);          // group_max's own operator
   return m;
 }
 template <typename T>
@@ -123,16 +98,6 @@ ZS_HD KlpqSums<T> klpq_lane_weights(const KlpqSide& p, const KlpqSide& q, int64_
     a.sq += w * w;
   }
   return a;
-}
-// The xor butterfly over G partials as one thread sees it (v[0 .. G) is overwritten; every entry ends as the group's value):
-// what the kernel's shuffles compute, for the host program.
-template <typename T, typename Op>
-inline void klpq_butterfly_host(T* v, int G, Op op) {
-  T t[ZS_KLPQ_WAVE];
-  for (int o = G >> 1; o > 0; o >>= 1) {
-    for (int l = 0; l < G; ++l) t[l] = op(v[l], v[l ^ o]);
-    for (int l = 0; l < G; ++l) v[l] = t[l];
-  }
 }
 
 // ---------------------------------------------------------------- the batch mean

@@ -21,22 +21,16 @@ namespace {
 
 constexpr int THREADS = ZS_MVN_THREADS;
 
-template <typename T>
-__device__ __forceinline__ T group_sum(T v, int G) {
-  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);
-  return v;
-}
-
 // the lower triangle of L[r] into the group's tile (the upper triangle is never read, neither here nor from the tile)
 template <typename T, int G>
-__device__ __forceinline__ void tile_load(T* tile, const T* __restrict__ Lr, const MvnPlace& pl, int D) {
-  for (MvnWalk w = mvn_walk_first(pl.i, D); w.i < D; mvn_walk_next(w, G, D))
+__device__ __forceinline__ void tile_load(T* tile, const T* __restrict__ Lr, const GroupPlace& pl, int D) {
+  for (MvnWalk w = mvn_walk_first(pl.lane, D); w.i < D; mvn_walk_next(w, G, D))
     if (w.j <= w.i) tile[mvn_tile_index(pl.grp, w.i, w.j, G)] = Lr[w.i * D + w.j];
 }
 // the group's tile out to a D x D matrix, zeros above the diagonal
 template <typename T, int G>
-__device__ __forceinline__ void tile_store(const T* tile, T* __restrict__ out, const MvnPlace& pl, int D) {
-  for (MvnWalk w = mvn_walk_first(pl.i, D); w.i < D; mvn_walk_next(w, G, D))
+__device__ __forceinline__ void tile_store(const T* tile, T* __restrict__ out, const GroupPlace& pl, int D) {
+  for (MvnWalk w = mvn_walk_first(pl.lane, D); w.i < D; mvn_walk_next(w, G, D))
     out[w.i * D + w.j] = w.j <= w.i ? tile[mvn_tile_index(pl.grp, w.i, w.j, G)] : (T)0;
 }
 
@@ -48,19 +42,19 @@ __device__ __forceinline__ T normal_at(int64_t flat, const PhiloxCall& pc) {
 
 // y = L^-1 b over the group: lane i enters with b_i and leaves with y_i (zs_mvn_math.h: mvn_forward_row)
 template <typename T, int G>
-__device__ __forceinline__ T forward_subst(const T* tile, const MvnPlace& pl, int D, T b, T rdiag) {
+__device__ __forceinline__ T forward_subst(const T* tile, const GroupPlace& pl, int D, T b, T rdiag) {
   for (int j = 0; j < D; ++j) {
     const T t = __shfl(mvn_solved(b, rdiag), pl.first + j, ZS_WAVE);
-    if (pl.i > j && pl.i < D) b = mvn_subst_step(b, tile[mvn_tile_index(pl.grp, pl.i, j, G)], t);
+    if (pl.lane > j && pl.lane < D) b = mvn_subst_step(b, tile[mvn_tile_index(pl.grp, pl.lane, j, G)], t);
   }
   return mvn_solved(b, rdiag);
 }
 // w = L^-T c over the group (mvn_backward_row)
 template <typename T, int G>
-__device__ __forceinline__ T backward_subst(const T* tile, const MvnPlace& pl, int D, T c, T rdiag) {
+__device__ __forceinline__ T backward_subst(const T* tile, const GroupPlace& pl, int D, T c, T rdiag) {
   for (int j = D - 1; j >= 0; --j) {
     const T t = __shfl(mvn_solved(c, rdiag), pl.first + j, ZS_WAVE);
-    if (pl.i < j) c = mvn_subst_step(c, tile[mvn_tile_index(pl.grp, j, pl.i, G)], t);
+    if (pl.lane < j) c = mvn_subst_step(c, tile[mvn_tile_index(pl.grp, j, pl.lane, G)], t);
   }
   return mvn_solved(c, rdiag);
 }
@@ -76,16 +70,16 @@ __global__ __launch_bounds__(THREADS) void k_mvn_forward(const T* __restrict__ m
   __shared__ T tile[THREADS * (G + 1)];
   if (rs) { seed = rs[0]; call += rs[1]; }
   const PhiloxCall pc = philox_call(call, seed);
-  const MvnPlace pl = mvn_place((int)threadIdx.x, G);
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
   const int64_t k0 = (int64_t)blockIdx.y * kshare, k1 = k0 + kshare < K ? k0 + kshare : K;
-  for (int64_t rb = mvn_row_first((int)blockIdx.x, pl); rb < R; rb += mvn_row_step((int)gridDim.x, pl)) {
+  for (int64_t rb = group_row_first((int)blockIdx.x, pl); rb < R; rb += group_row_step((int)gridDim.x, pl)) {
     const int64_t r = rb + pl.grp;
-    const bool valid = r < R, act = valid && pl.i < D;
+    const bool valid = r < R, act = valid && pl.lane < D;
     __syncthreads();
     if (valid) tile_load<T, G>(tile, tril + r * D * D, pl, D);
     __syncthreads();
-    const T m = act ? mean[r * D + pl.i] : (T)0;
-    const T diag = act ? tile[mvn_tile_index(pl.grp, pl.i, pl.i, G)] : (T)1;
+    const T m = act ? mean[r * D + pl.lane] : (T)0;
+    const T diag = act ? tile[mvn_tile_index(pl.grp, pl.lane, pl.lane, G)] : (T)1;
     const T rdiag = mvn_rdiag(diag);
     const T slog = group_sum(act ? mvn_log(diag) : (T)0, G);
     for (int64_t k = k0; k < k1; ++k) {
@@ -93,21 +87,21 @@ __global__ __launch_bounds__(THREADS) void k_mvn_forward(const T* __restrict__ m
       T y;
       if (SAMPLE) {
         y = (T)0;
-        if (act) y = in ? in[it * D + pl.i] : normal_at<T>(it * D + pl.i, pc);
+        if (act) y = in ? in[it * D + pl.lane] : normal_at<T>(it * D + pl.lane, pc);
         T acc = m;
         for (int j = 0; j < D; ++j) {
           const T ej = __shfl(y, pl.first + j, ZS_WAVE);
-          if (act && j <= pl.i) acc = mvn_matvec_step(acc, tile[mvn_tile_index(pl.grp, pl.i, j, G)], ej);
+          if (act && j <= pl.lane) acc = mvn_matvec_step(acc, tile[mvn_tile_index(pl.grp, pl.lane, j, G)], ej);
         }
-        if (act && z) z[it * D + pl.i] = acc;
+        if (act && z) z[it * D + pl.lane] = acc;
       } else {
         const int64_t xr = prow == R ? r : it;
-        const T b = act ? in[xr * D + pl.i] - m : (T)0;
+        const T b = act ? in[xr * D + pl.lane] - m : (T)0;
         y = forward_subst<T, G>(tile, pl, D, b, rdiag);
       }
       if (lp) {
         const T ss = group_sum(act ? y * y : (T)0, G);
-        if (valid && pl.i == 0) lp[it] = mvn_lp(c0, slog, ss);
+        if (valid && pl.lane == 0) lp[it] = mvn_lp(c0, slog, ss);
       }
     }
   }
@@ -127,16 +121,16 @@ __global__ __launch_bounds__(THREADS) void k_mvn_backward(const T* __restrict__ 
   __shared__ T tile[THREADS * (G + 1)];
   if (rs) { seed = rs[0]; call += rs[1]; }
   const PhiloxCall pc = philox_call(call, seed);
-  const MvnPlace pl = mvn_place((int)threadIdx.x, G);
-  for (int64_t rb = mvn_row_first((int)blockIdx.x, pl); rb < R; rb += mvn_row_step((int)gridDim.x, pl)) {
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  for (int64_t rb = group_row_first((int)blockIdx.x, pl); rb < R; rb += group_row_step((int)gridDim.x, pl)) {
     const int64_t r = rb + pl.grp;
-    const bool valid = r < R, act = valid && pl.i < D;
+    const bool valid = r < R, act = valid && pl.lane < D;
     const T* Lr = tril + r * D * D;
     __syncthreads();
     if (MODE != 0 && valid) tile_load<T, G>(tile, Lr, pl, D);
     __syncthreads();
-    const T m = (MODE == 2 && act) ? mean[r * D + pl.i] : (T)0;
-    const T rdiag = mvn_rdiag(act ? Lr[pl.i * D + pl.i] : (T)1);
+    const T m = (MODE == 2 && act) ? mean[r * D + pl.lane] : (T)0;
+    const T rdiag = mvn_rdiag(act ? Lr[pl.lane * D + pl.lane] : (T)1);
     T gm = (T)0, sg = (T)0, acc[G];
 #pragma unroll
     for (int j = 0; j < G; ++j) acc[j] = (T)0;
@@ -146,12 +140,12 @@ __global__ __launch_bounds__(THREADS) void k_mvn_backward(const T* __restrict__ 
       T y = (T)0, w;
       if (MODE == 2) {
         const int64_t xr = prow == R ? r : it;
-        y = forward_subst<T, G>(tile, pl, D, act ? in[xr * D + pl.i] - m : (T)0, rdiag);
+        y = forward_subst<T, G>(tile, pl, D, act ? in[xr * D + pl.lane] - m : (T)0, rdiag);
       } else if (act) {
-        y = in ? in[it * D + pl.i] : normal_at<T>(it * D + pl.i, pc);
+        y = in ? in[it * D + pl.lane] : normal_at<T>(it * D + pl.lane, pc);
       }
       if (MODE == 0) {
-        w = (gz && act) ? gz[it * D + pl.i] : (T)0;
+        w = (gz && act) ? gz[it * D + pl.lane] : (T)0;
         gm += w;
         sg += g;
 #pragma unroll
@@ -160,18 +154,18 @@ __global__ __launch_bounds__(THREADS) void k_mvn_backward(const T* __restrict__ 
       } else {
         w = backward_subst<T, G>(tile, pl, D, y, rdiag);
         gm = flat_fma(g, w, gm);
-        if (MODE == 2 && gx && act) gx[it * D + pl.i] = -g * w;
+        if (MODE == 2 && gx && act) gx[it * D + pl.lane] = -g * w;
 #pragma unroll
         for (int j = 0; j < G; ++j)
-          if (j < D) acc[j] = mvn_gtril_step(acc[j], g, w, __shfl(y, pl.first + j, ZS_WAVE), j == pl.i, rdiag);
+          if (j < D) acc[j] = mvn_gtril_step(acc[j], g, w, __shfl(y, pl.first + j, ZS_WAVE), j == pl.lane, rdiag);
       }
     }
-    if (gmean && act) gmean[r * D + pl.i] = gm;
+    if (gmean && act) gmean[r * D + pl.lane] = gm;
     if (gtril) {
       __syncthreads();          // the substitutions have finished with the tile
 #pragma unroll
       for (int j = 0; j < G; ++j)
-        if (act && j <= pl.i) tile[mvn_tile_index(pl.grp, pl.i, j, G)] = (MODE == 0 && j == pl.i) ? flat_fma(-sg, rdiag, acc[j]) : acc[j];
+        if (act && j <= pl.lane) tile[mvn_tile_index(pl.grp, pl.lane, j, G)] = (MODE == 0 && j == pl.lane) ? flat_fma(-sg, rdiag, acc[j]) : acc[j];
       __syncthreads();
       if (valid) tile_store<T, G>(tile, gtril + r * D * D, pl, D);
     }
@@ -207,7 +201,7 @@ double lp_c0(int64_t D) { return -0.5 * (double)D * 1.83787706640934548356065947
 template <typename T, bool SAMPLE>
 int forward(const void* mean, const void* tril, const void* in, int64_t prow, void* z, void* lp, int64_t K, int64_t R, int64_t D,
             uint64_t seed, uint64_t call, const uint64_t* rs, void* stream) {
-  const int G = mvn_group_lanes(D);
+  const int G = group_lanes(D);
   const unsigned gx = row_blocks(R, G);
   // enough workgroups to fill the chip when the rows alone do not: the particles are cut into contiguous shares
   int64_t shares = (2048 + gx - 1) / gx;
@@ -225,7 +219,7 @@ int forward(const void* mean, const void* tril, const void* in, int64_t prow, vo
 template <typename T, int MODE>
 int backward(const void* mean, const void* tril, const void* in, int64_t prow, const void* gz, const void* glp, void* gx, void* gmean,
              void* gtril, int64_t K, int64_t R, int64_t D, uint64_t seed, uint64_t call, const uint64_t* rs, void* stream) {
-  const int G = mvn_group_lanes(D);
+  const int G = group_lanes(D);
   ZS_MVN_BY_G(G, hipLaunchKernelGGL((k_mvn_backward<T, GG, MODE>), dim3(row_blocks(R, G)), dim3(THREADS), 0, (hipStream_t)stream,
                                     (const T*)mean, (const T*)tril, (const T*)in, prow, (const T*)gz, (const T*)glp, (T*)gx,
                                     (T*)gmean, (T*)gtril, K, R, (int)D, seed, call, rs));
@@ -282,7 +276,7 @@ int mvn_logprob_bwd(const void* mean, const void* tril, const void* x, int64_t P
 
 extern "C" int zs_mvn_abi_version(void) { return ZS_MVN_ABI_VERSION; }
 extern "C" int zs_mvn_max_dim(void) { return ZS_MVN_MAX_DIM; }
-extern "C" int zs_mvn_group_lanes(int64_t D) { return (D < 1 || D > ZS_MVN_MAX_DIM) ? 0 : mvn_group_lanes(D); }
+extern "C" int zs_mvn_group_lanes(int64_t D) { return (D < 1 || D > ZS_MVN_MAX_DIM) ? 0 : group_lanes(D); }
 
 #define ZS_MVN_ENTRY(SFX, T)                                                                                                        \
   extern "C" int zs_mvn_sample_logprob##SFX(const void* mean, const void* tril, const void* eps, void* z, void* lp, int64_t K,      \

@@ -1,10 +1,10 @@
-// The arithmetic and the lane map of the multivariate-normal kernels (include/zs_mvn.h, zs_mvn.hip): the lane group of a row,
-// the walk of a group over the lower triangle, the place of an element of L in the group's LDS tile, and the steps of the matvec,
-// of the two substitutions and of the density.  __host__ __device__, so that tests/host_math/zs_mvn_host_math.hip walks the same
-// code on the host under the sanitizers.
+// The arithmetic of the multivariate-normal kernels (include/zs_mvn.h, zs_mvn.hip) and what they add to the lane-group map of
+// zs_group_math.h: the walk of a group over the lower triangle, the place of an element of L in the group's LDS tile, and the
+// steps of the matvec, of the two substitutions and of the density.  __host__ __device__, so that
+// tests/host_math/zs_mvn_host_math.hip walks the same code on the host under the sanitizers.
 #pragma once
 #include <math.h>
-#include "zs_flat_math.h"
+#include "zs_group_math.h"
 
 // a * b + c rounds once only where flat_fma says so: the same bits whatever the alignment of the operands
 #pragma clang fp contract(off)
@@ -18,32 +18,9 @@ ZS_HD float mvn_log(float x) { return logf(x); }
 ZS_HD double mvn_log(double x) { return log(x); }
 
 // ---------------------------------------------------------------- lane groups
-// A group of G = next_pow2(D) consecutive lanes of one wave owns a row of the batch (mean[r, :], tril[r, :, :]); lane i < D of
-// the group owns component i: element i of every vector and row i of every triangular accumulator.  A wave holds 64 / G rows.
-ZS_HD int mvn_group_lanes(int64_t D) {
-  int g = 1;
-  while (g < ZS_MVN_MAX_DIM && g < D) g <<= 1;
-  return g;
-}
-struct MvnPlace {
-  int i;            // lane within the group = the component it owns (idle when i >= D)
-  int first;        // the group's first lane within the wave
-  int grp;          // the group within the wave
-  int groups;       // groups per wave = rows per workgroup
-};
-ZS_HD MvnPlace mvn_place(int thread, int G) {
-  MvnPlace p;
-  p.i = thread & (G - 1);
-  p.first = thread & ~(G - 1);
-  p.grp = thread / G;
-  p.groups = ZS_MVN_THREADS / G;
-  return p;
-}
-// The rows of a workgroup, as every kernel walks them -- the trip count is the same for all lanes of the wave, a group past the
-// last row idles through the exchanges and stores nothing:
-//   for (int64_t rb = mvn_row_first(block, pl); rb < R; rb += mvn_row_step(blocks, pl)) { r = rb + pl.grp; valid = r < R; ... }
-ZS_HD int64_t mvn_row_first(int block, const MvnPlace& p) { return (int64_t)block * p.groups; }
-ZS_HD int64_t mvn_row_step(int blocks, const MvnPlace& p) { return (int64_t)blocks * p.groups; }
+// A group of G = group_lanes(D) consecutive lanes of one wave owns a row of the batch (mean[r, :], tril[r, :, :]); lane
+// pl.lane = i < D of the group owns component i: element i of every vector and row i of every triangular accumulator (idle when
+// i >= D).  A wave holds 64 / G rows; the place and the row loop are zs_group_math.h's, with ZS_MVN_THREADS threads.
 
 // The walk of lane `lane` of a group over the D x D elements of a row-major matrix, G consecutive elements per step (the group's
 // accesses are contiguous):   for (MvnWalk w = mvn_walk_first(lane, D); w.i < D; mvn_walk_next(w, G, D))

@@ -22,12 +22,6 @@ constexpr int THREADS = ZS_NF_THREADS;
 
 extern __shared__ __align__(16) unsigned char nf_lds_raw[];
 
-template <typename T>
-__device__ __forceinline__ T group_sum(T v, int G) {
-  for (int o = G >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);
-  return v;
-}
-
 // The parameter quantities of layer l over one wave: lane d < D holds u_l[d], w_l[d], uh_l[d]; s, n, k, c are the same in all lanes.
 template <typename T>
 struct NfLayer { T u, w, s, n, k, uh, c; };
@@ -63,28 +57,28 @@ __global__ __launch_bounds__(THREADS) void k_planar_fwd(const T* __restrict__ u,
   T* cc = uh + L * D;
   planar_stack_to_lds(u, w, uh, cc, D, L);
   __syncthreads();
-  const NfPlace pl = nf_place((int)threadIdx.x, G);
-  for (int64_t rb = nf_row_first((int)blockIdx.x, pl); rb < R; rb += nf_row_step((int)gridDim.x, pl)) {
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  for (int64_t rb = group_row_first((int)blockIdx.x, pl); rb < R; rb += group_row_step((int)gridDim.x, pl)) {
     const int64_t r = rb + pl.grp;
-    const bool valid = r < R, act = valid && pl.i < D;
-    T z = act ? x[r * D + pl.i] : (T)0, ld = (T)0;
+    const bool valid = r < R, act = valid && pl.lane < D;
+    T z = act ? x[r * D + pl.lane] : (T)0, ld = (T)0;
     for (int l = 0; l < L; ++l) {
-      const T wd = act ? w[l * D + pl.i] : (T)0;
+      const T wd = act ? w[l * D + pl.lane] : (T)0;
       const T t = nf_planar_t(group_sum(wd * z, G), b[l]);
-      if (act) z = nf_planar_z(z, uh[l * D + pl.i], t);
+      if (act) z = nf_planar_z(z, uh[l * D + pl.lane], t);
       ld = nf_planar_logdet(ld, t, cc[l]);
     }
-    if (act && y) y[r * D + pl.i] = z;
-    if (valid && pl.i == 0 && logdet) logdet[r] = ld;
+    if (act && y) y[r * D + pl.lane] = z;
+    if (valid && pl.lane == 0 && logdet) logdet[r] = ld;
   }
 }
 
 // ---------------------------------------------------------------- P1b
-// this tile's sum of `v` over the groups of the wave in ascending group (= row) order, for component pl.i
+// this tile's sum of `v` over the groups of the wave in ascending group (= row) order, for component pl.lane
 template <typename T>
-__device__ __forceinline__ T tile_sum(T v, const NfPlace& pl, int G) {
-  T s = __shfl(v, pl.i, ZS_WAVE);
-  for (int gi = 1; gi < pl.groups; ++gi) s += __shfl(v, gi * G + pl.i, ZS_WAVE);
+__device__ __forceinline__ T tile_sum(T v, const GroupPlace& pl, int G) {
+  T s = __shfl(v, pl.lane, ZS_WAVE);
+  for (int gi = 1; gi < pl.groups; ++gi) s += __shfl(v, gi * G + pl.lane, ZS_WAVE);
   return s;
 }
 
@@ -93,32 +87,32 @@ __global__ __launch_bounds__(THREADS) void k_planar_bwd(const T* __restrict__ u,
                                                         const T* __restrict__ x, const T* __restrict__ gy, const T* __restrict__ gld,
                                                         T* __restrict__ gx, T* partials, int64_t R, int D, int L, int G) {
   const int lane = (int)threadIdx.x;
-  const NfPlace pl = nf_place(lane, G);
+  const GroupPlace pl = group_place(lane, THREADS, G);
   T* uh = reinterpret_cast<T*>(nf_lds_raw);
   T* cc = uh + L * D;
   T* ts = cc + L;
   T* zin = ts + L * pl.groups;
   planar_stack_to_lds(u, w, uh, cc, D, L);
-  const int64_t rb0 = nf_row_first((int)blockIdx.x, pl);
-  for (int64_t rb = rb0; rb < R; rb += nf_row_step((int)gridDim.x, pl)) {
+  const int64_t rb0 = group_row_first((int)blockIdx.x, pl);
+  for (int64_t rb = rb0; rb < R; rb += group_row_step((int)gridDim.x, pl)) {
     const int64_t r = rb + pl.grp;
-    const bool valid = r < R, act = valid && pl.i < D;
+    const bool valid = r < R, act = valid && pl.lane < D;
     __syncthreads();          // uh, c are in place; the previous tile has finished with ts
     // the forward again, with the forward's own device functions: the same a_l, z_l bit for bit
-    T z = act ? x[r * D + pl.i] : (T)0;
+    T z = act ? x[r * D + pl.lane] : (T)0;
     for (int l = 0; l < L; ++l) {
       zin[nf_z_index(l, lane)] = z;
-      const T wd = act ? w[l * D + pl.i] : (T)0;
+      const T wd = act ? w[l * D + pl.lane] : (T)0;
       const T t = nf_planar_t(group_sum(wd * z, G), b[l]);
-      if (pl.i == 0) ts[nf_t_index(l, pl.grp, pl.groups)] = t;
-      if (act) z = nf_planar_z(z, uh[l * D + pl.i], t);
+      if (pl.lane == 0) ts[nf_t_index(l, pl.grp, pl.groups)] = t;
+      if (act) z = nf_planar_z(z, uh[l * D + pl.lane], t);
     }
     __syncthreads();
-    T g = (gy && act) ? gy[r * D + pl.i] : (T)0;
+    T g = (gy && act) ? gy[r * D + pl.lane] : (T)0;
     const T gl = (gld && valid) ? gld[r] : (T)0;
     for (int l = L - 1; l >= 0; --l) {
       const T t = ts[nf_t_index(l, pl.grp, pl.groups)], c = cc[l];
-      const T uhd = act ? uh[l * D + pl.i] : (T)0, wd = act ? w[l * D + pl.i] : (T)0;
+      const T uhd = act ? uh[l * D + pl.lane] : (T)0, wd = act ? w[l * D + pl.lane] : (T)0;
       const T zl = zin[nf_z_index(l, lane)];
       const T h = nf_planar_h(t), m = nf_planar_m(h, c);
       const T ga = nf_planar_gt(group_sum(g * uhd, G), gl, c, m, t) * h;
@@ -128,9 +122,9 @@ __global__ __launch_bounds__(THREADS) void k_planar_bwd(const T* __restrict__ u,
         const T sb = tile_sum(valid ? ga : (T)0, pl, G);
         const T sc = tile_sum(valid ? nf_planar_gc(gl, h, m) : (T)0, pl, G);
         T* P = partials + nf_partial_row((int64_t)blockIdx.x, l, D, L);
-        if (pl.grp == 0 && pl.i < D) {
-          T* pu = P + nf_partial_guh(pl.i);
-          T* pw = P + nf_partial_gw(pl.i, D);
+        if (pl.grp == 0 && pl.lane < D) {
+          T* pu = P + nf_partial_guh(pl.lane);
+          T* pw = P + nf_partial_gw(pl.lane, D);
           *pu = rb == rb0 ? su : *pu + su;
           *pw = rb == rb0 ? sw : *pw + sw;
         }
@@ -143,7 +137,7 @@ __global__ __launch_bounds__(THREADS) void k_planar_bwd(const T* __restrict__ u,
       }
       if (act) g = nf_planar_g(g, ga, wd);
     }
-    if (gx && act) gx[r * D + pl.i] = g;
+    if (gx && act) gx[r * D + pl.lane] = g;
   }
 }
 
@@ -204,17 +198,17 @@ __global__ __launch_bounds__(ZS_NF_FINISH_THREADS) void k_planar_finish(const T*
 // ---------------------------------------------------------------- H1, H1b
 template <typename T>
 __global__ __launch_bounds__(THREADS) void k_householder_fwd(const T* __restrict__ v, const T* x, T* y, int64_t R, int D, int L, int G) {
-  const NfPlace pl = nf_place((int)threadIdx.x, G);
-  for (int64_t rb = nf_row_first((int)blockIdx.x, pl); rb < R; rb += nf_row_step((int)gridDim.x, pl)) {
+  const GroupPlace pl = group_place((int)threadIdx.x, THREADS, G);
+  for (int64_t rb = group_row_first((int)blockIdx.x, pl); rb < R; rb += group_row_step((int)gridDim.x, pl)) {
     const int64_t r = rb + pl.grp;
-    const bool act = r < R && pl.i < D;
-    T z = act ? x[r * D + pl.i] : (T)0;
+    const bool act = r < R && pl.lane < D;
+    T z = act ? x[r * D + pl.lane] : (T)0;
     for (int l = 0; l < L; ++l) {
-      const T vd = act ? v[((int64_t)l * R + r) * D + pl.i] : (T)0;
+      const T vd = act ? v[((int64_t)l * R + r) * D + pl.lane] : (T)0;
       const T n = group_sum(vd * vd, G), p = group_sum(vd * z, G);
       if (act) z = nf_householder_z(z, vd, p, n);
     }
-    if (act) y[r * D + pl.i] = z;
+    if (act) y[r * D + pl.lane] = z;
   }
 }
 
@@ -223,27 +217,27 @@ __global__ __launch_bounds__(THREADS) void k_householder_bwd(const T* __restrict
                                                              T* __restrict__ gx, T* __restrict__ gv, int64_t R, int D, int L, int G) {
   T* zin = reinterpret_cast<T*>(nf_lds_raw);
   const int lane = (int)threadIdx.x;
-  const NfPlace pl = nf_place(lane, G);
-  for (int64_t rb = nf_row_first((int)blockIdx.x, pl); rb < R; rb += nf_row_step((int)gridDim.x, pl)) {
+  const GroupPlace pl = group_place(lane, THREADS, G);
+  for (int64_t rb = group_row_first((int)blockIdx.x, pl); rb < R; rb += group_row_step((int)gridDim.x, pl)) {
     const int64_t r = rb + pl.grp;
-    const bool act = r < R && pl.i < D;
-    T z = act ? x[r * D + pl.i] : (T)0;
+    const bool act = r < R && pl.lane < D;
+    T z = act ? x[r * D + pl.lane] : (T)0;
     for (int l = 0; l < L; ++l) {
       zin[nf_z_index(l, lane)] = z;          // read back below by this lane only
-      const T vd = act ? v[((int64_t)l * R + r) * D + pl.i] : (T)0;
+      const T vd = act ? v[((int64_t)l * R + r) * D + pl.lane] : (T)0;
       const T n = group_sum(vd * vd, G), p = group_sum(vd * z, G);
       if (act) z = nf_householder_z(z, vd, p, n);
     }
-    T g = act ? gy[r * D + pl.i] : (T)0;
+    T g = act ? gy[r * D + pl.lane] : (T)0;
     for (int l = L - 1; l >= 0; --l) {
-      const int64_t at = ((int64_t)l * R + r) * D + pl.i;
+      const int64_t at = ((int64_t)l * R + r) * D + pl.lane;
       const T vd = act ? v[at] : (T)0;
       const T zl = zin[nf_z_index(l, lane)];
       const T n = group_sum(vd * vd, G), p = group_sum(vd * zl, G), q = group_sum(vd * g, G);
       if (act && gv) gv[at] = nf_householder_gv(g, zl, vd, p, q, n);
       if (act) g = nf_householder_z(g, vd, q, n);
     }
-    if (act && gx) gx[r * D + pl.i] = g;
+    if (act && gx) gx[r * D + pl.lane] = g;
   }
 }
 
@@ -262,7 +256,7 @@ int planar_fwd(const void* u, const void* w, const void* b, const void* x, void*
   if (rc) return rc;
   if (R == 0 || L == 0) return 0;
   if (!y && !logdet) return ZS_EINVAL;
-  const int G = nf_group_lanes(D);
+  const int G = group_lanes(D);
   hipLaunchKernelGGL((k_planar_fwd<T>), dim3(nf_workgroups(R, G)), dim3(THREADS), (size_t)nf_planar_fwd_lds(D, L) * sizeof(T),
                      (hipStream_t)stream, (const T*)u, (const T*)w, (const T*)b, (const T*)x, (T*)y, (T*)logdet, R, (int)D, (int)L, G);
   ZS_CHECK_LAUNCH();
@@ -277,7 +271,7 @@ int planar_bwd(const void* u, const void* w, const void* b, const void* x, const
   if (rc) return rc;
   if (R == 0 || L == 0) return 0;
   if ((!gy && !gld) || (!gx && !partials)) return ZS_EINVAL;
-  const int G = nf_group_lanes(D);
+  const int G = group_lanes(D);
   hipLaunchKernelGGL((k_planar_bwd<T>), dim3(nf_workgroups(R, G)), dim3(THREADS), (size_t)nf_planar_bwd_lds(D, L, G) * sizeof(T),
                      (hipStream_t)stream, (const T*)u, (const T*)w, (const T*)b, (const T*)x, (const T*)gy, (const T*)gld, (T*)gx,
                      (T*)partials, R, (int)D, (int)L, G);
@@ -306,7 +300,7 @@ int householder_fwd(const void* v, const void* x, void* y, int64_t R, int64_t D,
   if (rc) return rc;
   if (R == 0 || L == 0) return 0;
   if (!y) return ZS_EINVAL;
-  const int G = nf_group_lanes(D);
+  const int G = group_lanes(D);
   hipLaunchKernelGGL((k_householder_fwd<T>), dim3(nf_workgroups(R, G)), dim3(THREADS), 0, (hipStream_t)stream, (const T*)v,
                      (const T*)x, (T*)y, R, (int)D, (int)L, G);
   ZS_CHECK_LAUNCH();
@@ -320,7 +314,7 @@ int householder_bwd(const void* v, const void* x, const void* gy, void* gx, void
   if (rc) return rc;
   if (R == 0 || L == 0) return 0;
   if (!gx && !gv) return ZS_EINVAL;
-  const int G = nf_group_lanes(D);
+  const int G = group_lanes(D);
   hipLaunchKernelGGL((k_householder_bwd<T>), dim3(nf_workgroups(R, G)), dim3(THREADS), (size_t)nf_householder_bwd_lds(L) * sizeof(T),
                      (hipStream_t)stream, (const T*)v, (const T*)x, (const T*)gy, (T*)gx, (T*)gv, R, (int)D, (int)L, G);
   ZS_CHECK_LAUNCH();
@@ -333,9 +327,9 @@ extern "C" int zs_nf_abi_version(void) { return ZS_NF_ABI_VERSION; }
 extern "C" int zs_nf_max_dim(void) { return ZS_NF_MAX_DIM; }
 extern "C" int zs_nf_max_layers(void) { return ZS_NF_MAX_LAYERS; }
 extern "C" int zs_nf_max_workgroups(void) { return ZS_NF_MAX_WORKGROUPS; }
-extern "C" int zs_nf_group_lanes(int64_t D) { return (D < 1 || D > ZS_NF_MAX_DIM) ? 0 : nf_group_lanes(D); }
+extern "C" int zs_nf_group_lanes(int64_t D) { return (D < 1 || D > ZS_NF_MAX_DIM) ? 0 : group_lanes(D); }
 extern "C" int zs_nf_planar_workgroups(int64_t R, int64_t D) {
-  return (R < 1 || D < 1 || D > ZS_NF_MAX_DIM) ? 0 : nf_workgroups(R, nf_group_lanes(D));
+  return (R < 1 || D < 1 || D > ZS_NF_MAX_DIM) ? 0 : nf_workgroups(R, group_lanes(D));
 }
 
 #define ZS_NF_ENTRY(SFX, T)                                                                                                          \

@@ -1,10 +1,10 @@
-// The arithmetic and the lane map of the planar / Householder flow kernels (include/zs_nf.h, zs_nf.hip): the lane group of a
-// row, the LDS places of the layer inputs z_l, the place of a workgroup's partial sums, and the steps of a layer, of its backward
-// and of the parameter chain.  __host__ __device__, so that tests/host_math/zs_nf_host_math.hip walks the same code on the host
-// under the sanitizers.
+// The arithmetic of the planar / Householder flow kernels (include/zs_nf.h, zs_nf.hip) and what they add to the lane-group map
+// of zs_group_math.h: the LDS places of the layer inputs z_l, the place of a workgroup's partial sums, and the steps of a layer,
+// of its backward and of the parameter chain.  __host__ __device__, so that tests/host_math/zs_nf_host_math.hip walks the same
+// code on the host under the sanitizers.
 #pragma once
 #include <math.h>
-#include "zs_flat_math.h"
+#include "zs_group_math.h"
 
 // one rounding per written operation: nothing here is contracted into an fma
 #pragma clang fp contract(off)
@@ -29,36 +29,10 @@ ZS_HD float nf_abs(float x) { return fabsf(x); }
 ZS_HD double nf_abs(double x) { return fabs(x); }
 
 // ---------------------------------------------------------------- lane groups and row tiles
-// A group of G = next_pow2(D) consecutive lanes of one wave owns a row; lane i < D of the group owns component i.
-ZS_HD int nf_group_lanes(int64_t D) {
-  int g = 1;
-  while (g < ZS_NF_MAX_DIM && g < D) g <<= 1;
-  return g;
-}
-struct NfPlace {
-  int i;            // lane within the group = the component it owns (idle when i >= D)
-  int first;        // the group's first lane within the wave
-  int grp;          // the group within the wave
-  int groups;       // groups per wave = rows per tile
-};
-ZS_HD NfPlace nf_place(int thread, int G) {
-  NfPlace p;
-  p.i = thread & (G - 1);
-  p.first = thread & ~(G - 1);
-  p.grp = thread / G;
-  p.groups = ZS_NF_THREADS / G;
-  return p;
-}
-// The row tiles of a workgroup -- the trip count is the same for all lanes of the wave, a group past the last row idles through
-// the exchanges and stores nothing:
-//   for (int64_t rb = nf_row_first(block, pl); rb < R; rb += nf_row_step(blocks, pl)) { r = rb + pl.grp; valid = r < R; ... }
-ZS_HD int64_t nf_row_first(int block, const NfPlace& p) { return (int64_t)block * p.groups; }
-ZS_HD int64_t nf_row_step(int blocks, const NfPlace& p) { return (int64_t)blocks * p.groups; }
-// workgroups for R >= 1 rows in groups of G lanes
-ZS_HD int nf_workgroups(int64_t R, int G) {
-  const int64_t per = ZS_NF_THREADS / G, b = (R + per - 1) / per;
-  return b > ZS_NF_MAX_WORKGROUPS ? ZS_NF_MAX_WORKGROUPS : (int)(b < 1 ? 1 : b);
-}
+// A group of G = group_lanes(D) consecutive lanes of one wave owns a row; lane pl.lane = i < D of the group owns component i
+// (idle when i >= D).  The place and the row tiles of a workgroup are zs_group_math.h's, with ZS_NF_THREADS threads.
+// workgroups for R >= 1 rows in groups of G lanes = the leading extent of the partials
+ZS_HD int nf_workgroups(int64_t R, int G) { return group_workgroups(R, G, ZS_NF_THREADS, ZS_NF_MAX_WORKGROUPS); }
 
 // LDS of a backward workgroup: lane `thread` keeps the input z_l of its row's layer l at nf_z_index (read back by the same lane);
 // the group's tanh of layer l sits at nf_t_index (planar only).  Planar: uh[L D], c[L], t[L groups], z[L 64]; Householder: z[L 64].
