@@ -11,14 +11,10 @@ import pytest
 import torch
 
 import cat_host
+from kernel_abi import DEV, EINVAL, ENOTSUP, F32, F64, I64, Arena, load, load_main, ptr, same_bits, sfx, stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-EINVAL, ENOTSUP = -1, -2
-GUARD = 4
-SENTINEL = 777.0
-F32, F64, I64 = torch.float32, torch.float64, torch.int64
 NS = [1, 2, 3, 4, 5, 31, 32, 33, 63, 64, 65, 127, 257, 1000, 4099]
 RS = [1, 3, 65]
 KS = [1, 2, 5]
@@ -67,74 +63,12 @@ def undecided(logits, u):
 # ------------------------------------------------------------------------------------------------ device plumbing
 @pytest.fixture(scope="module")
 def lib():
-    from zhusuan import _cat_hip
-    return _cat_hip.lib(_cat_hip.LIB_PATH)
+    return load("cat")
 
 
 @pytest.fixture(scope="module")
 def main_lib():
-    from zhusuan import _hip
-    return _hip.KernelLibrary(_hip.LIB_PATH)
-
-
-def _ptr(t):
-    return None if t is None else (t if isinstance(t, int) else t.data_ptr())
-
-
-def _stream():
-    from zhusuan import _hip
-    return _hip.stream_for(torch.empty(0, device=DEV))
-
-
-def sfx(dtype):
-    return "_f32" if dtype == F32 else "_f64"
-
-
-class Arena(object):
-    """Device operands inside guarded buffers: GUARD sentinels on both sides, `shift` more elements in front."""
-
-    def __init__(self, shift):
-        self.shift = shift
-        self.outs = []
-
-    def _buf(self, n, dtype):
-        o = GUARD + self.shift
-        fill = SENTINEL if dtype != I64 else 777
-        buf = torch.full((o + n + GUARD,), fill, dtype=dtype, device=DEV)
-        return buf, o
-
-    def put(self, t, dtype=None):
-        if t is None:
-            return None
-        t = t.to(dtype) if dtype is not None else t
-        buf, o = self._buf(t.numel(), t.dtype)
-        buf[o:o + t.numel()] = t.reshape(-1).to(DEV)
-        return buf[o:o + t.numel()]
-
-    def out(self, n, dtype):
-        buf, o = self._buf(n, dtype)
-        self.outs.append((buf, o, n))
-        return buf[o:o + n]
-
-    def check_guards(self):
-        for buf, o, n in self.outs:
-            s = SENTINEL if buf.dtype != I64 else 777
-            assert bool((buf[:o] == s).all()) and bool((buf[o + n:] == s).all()), "write outside the tensor"
-
-
-def untouched(v):
-    s = SENTINEL if v.dtype != I64 else 777
-    return bool((v == s).all())
-
-
-def same_bits(a, b):
-    if a is None and b is None:
-        return True
-    a, b = a.cpu(), b.cpu()
-    if a.dtype == I64:
-        return torch.equal(a, b)
-    it = torch.int32 if a.dtype == F32 else torch.int64
-    return torch.equal(a.view(it), b.view(it))
+    return load_main()
 
 
 def assert_close(name, got, truth, tol):
@@ -172,15 +106,15 @@ def c1(lib, dtype, ar, logits, u, K, R, N, want=(True, True, True), seed=0, call
     idx = ar.out(K * R, I64) if want[0] else None
     oh = ar.out(K * R * N, dtype) if want[1] else None
     lp = ar.out(K * R, dtype) if want[2] else None
-    rc = lib.raw("zs_cat_sample_logprob" + sfx(dtype), _ptr(logits), _ptr(u), _ptr(idx), _ptr(oh), _ptr(lp), K, R, N, seed, call,
-                 _ptr(rs), _stream())
+    rc = lib.raw("zs_cat_sample_logprob" + sfx(dtype), ptr(logits), ptr(u), ptr(idx), ptr(oh), ptr(lp), K, R, N, seed, call,
+                 ptr(rs), stream())
     return rc, idx, oh, lp
 
 
 def c2(lib, dtype, ar, logits, idx, x, K, R, N):
     lp = ar.out(K * R, dtype)
     v = idx if x is None else x
-    rc = lib.raw("zs_cat_logprob" + sfx(dtype), _ptr(logits), _ptr(idx), _ptr(x), v.numel(), _ptr(lp), K, R, N, _stream())
+    rc = lib.raw("zs_cat_logprob" + sfx(dtype), ptr(logits), ptr(idx), ptr(x), v.numel(), ptr(lp), K, R, N, stream())
     return rc, lp
 
 
@@ -188,8 +122,8 @@ def c2b(lib, dtype, ar, logits, idx, x, g, K, R, N, want_gx):
     gl = ar.out(R * N, dtype)
     gx = ar.out(K * R * N, dtype) if want_gx else None
     v = idx if x is None else x
-    rc = lib.raw("zs_cat_logprob_bwd" + sfx(dtype), _ptr(logits), _ptr(idx), _ptr(x), v.numel(), _ptr(g), _ptr(gl), _ptr(gx), K, R, N,
-                 _stream())
+    rc = lib.raw("zs_cat_logprob_bwd" + sfx(dtype), ptr(logits), ptr(idx), ptr(x), v.numel(), ptr(g), ptr(gl), ptr(gx), K, R, N,
+                 stream())
     return rc, gl, gx
 
 
@@ -197,30 +131,30 @@ def c3(lib, dtype, ar, logits, u, tau, exp_space, K, R, N, seed=0, call=0, rs=No
     y = ar.out(K * R * N, dtype)
     ey = ar.out(K * R * N, dtype) if exp_space else None
     lp = ar.out(K * R, dtype)
-    rc = lib.raw("zs_cat_expconcrete_sample_logprob" + sfx(dtype), _ptr(logits), _ptr(u), tau, exp_space, _ptr(y), _ptr(ey), _ptr(lp),
-                 K, R, N, seed, call, _ptr(rs), _stream())
+    rc = lib.raw("zs_cat_expconcrete_sample_logprob" + sfx(dtype), ptr(logits), ptr(u), tau, exp_space, ptr(y), ptr(ey), ptr(lp),
+                 K, R, N, seed, call, ptr(rs), stream())
     return rc, y, ey, lp
 
 
 def c3b(lib, dtype, ar, logits, y, tau, exp_space, gy, gey, glp, K, R, N):
     gl = ar.out(R * N, dtype)
-    rc = lib.raw("zs_cat_expconcrete_sample_logprob_bwd" + sfx(dtype), _ptr(logits), _ptr(y), tau, exp_space, _ptr(gy), _ptr(gey),
-                 _ptr(glp), _ptr(gl), K, R, N, _stream())
+    rc = lib.raw("zs_cat_expconcrete_sample_logprob_bwd" + sfx(dtype), ptr(logits), ptr(y), tau, exp_space, ptr(gy), ptr(gey),
+                 ptr(glp), ptr(gl), K, R, N, stream())
     return rc, gl
 
 
 def c4(lib, dtype, ar, logits, y, tau, exp_space, K, R, N):
     lp = ar.out(K * R, dtype)
-    rc = lib.raw("zs_cat_expconcrete_logprob" + sfx(dtype), _ptr(logits), _ptr(y), y.numel(), tau, exp_space, _ptr(lp), K, R, N,
-                 _stream())
+    rc = lib.raw("zs_cat_expconcrete_logprob" + sfx(dtype), ptr(logits), ptr(y), y.numel(), tau, exp_space, ptr(lp), K, R, N,
+                 stream())
     return rc, lp
 
 
 def c4b(lib, dtype, ar, logits, y, tau, exp_space, glp, K, R, N):
     gy = ar.out(K * R * N, dtype)
     gl = ar.out(R * N, dtype)
-    rc = lib.raw("zs_cat_expconcrete_logprob_bwd" + sfx(dtype), _ptr(logits), _ptr(y), y.numel(), tau, exp_space, _ptr(glp), _ptr(gy),
-                 _ptr(gl), K, R, N, _stream())
+    rc = lib.raw("zs_cat_expconcrete_logprob_bwd" + sfx(dtype), ptr(logits), ptr(y), y.numel(), tau, exp_space, ptr(glp), ptr(gy),
+                 ptr(gl), K, R, N, stream())
     return rc, gy, gl
 
 
@@ -261,7 +195,6 @@ def check_draw_and_log_mass(lib, N, R, K, scale, dtypes=(F32, F64), shifts=(0, 1
             rc3, lpw = c2(lib, dtype, ar, dl, None, dw, K, R, N)
             rc4, lpoh = c2(lib, dtype, ar, dl, None, oh, K, R, N)
             assert rc == 0 and rc2 == 0 and rc3 == 0 and rc4 == 0
-            torch.cuda.synchronize()
             ar.check_guards()
             assert same_bits(idx, idx_b) and same_bits(oh, oh_b) and same_bits(lp, lp_b)
             res.append((idx.cpu(), oh.cpu(), lp.cpu(), lp2.cpu(), lpw.cpu(), lpoh.cpu()))
@@ -315,7 +248,6 @@ def test_value_without_the_particle_axis_is_shared(lib):
             for e in (0, 1):
                 pairs.append((c4(lib, dtype, ar, dl, one, tau, e, K, R, N), c4(lib, dtype, ar, dl, full, tau, e, K, R, N)))
                 pairs.append((c4b(lib, dtype, ar, dl, one, tau, e, dg, K, R, N), c4b(lib, dtype, ar, dl, full, tau, e, dg, K, R, N)))
-            torch.cuda.synchronize()
             ar.check_guards()
             for got, want in pairs:
                 assert got[0] == 0 and want[0] == 0
@@ -331,16 +263,15 @@ def test_drawn_noise_is_the_main_librarys_uniform_stream(lib, main_lib, N):
     for dtype in (F32, F64):
         for seed, call, state in ((11, 3, None), (0, 2, (77, 1 << 33))):
             rs = None if state is None else torch.tensor(state, dtype=I64, device=DEV)
-            stream = torch.empty(n, dtype=F32, device=DEV)
-            main_lib.call("zs_philox_uniform_f32", stream.data_ptr(), n, seed, call, _ptr(rs), _stream())
+            noise = torch.empty(n, dtype=F32, device=DEV)
+            main_lib.call("zs_philox_uniform_f32", noise.data_ptr(), n, seed, call, ptr(rs), stream())
             for shift in (0, 1):
                 ar = Arena(shift)
-                dl, du = ar.put(lg, dtype), ar.put(stream.cpu(), dtype)
+                dl, du = ar.put(lg, dtype), ar.put(noise.cpu(), dtype)
                 drawn = c1(lib, dtype, ar, dl, None, K, R, N, seed=seed, call=call, rs=rs)
                 given = c1(lib, dtype, ar, dl, du, K, R, N)
                 rdrawn = c3(lib, dtype, ar, dl, None, 0.5, 1, K, R, N, seed=seed, call=call, rs=rs)
                 rgiven = c3(lib, dtype, ar, dl, du, 0.5, 1, K, R, N)
-                torch.cuda.synchronize()
                 ar.check_guards()
                 for a, b in list(zip(drawn, given)) + list(zip(rdrawn, rgiven)):
                     if isinstance(a, int):
@@ -380,7 +311,6 @@ def check_relaxed_draw_and_density(lib, N, R, K, scale, tau, exp_space, dtypes=(
             rc1, y_b, ey_b, lp_b = c3(lib, dtype, ar, dl, du, tau, exp_space, K, R, N)
             rc2, lp4 = c4(lib, dtype, ar, dl, y, tau, exp_space, K, R, N)
             assert rc == 0 and rc1 == 0 and rc2 == 0
-            torch.cuda.synchronize()
             ar.check_guards()
             assert same_bits(y, y_b) and same_bits(ey, ey_b) and same_bits(lp, lp_b)
             res.append((y.cpu(), None if ey is None else ey.cpu(), lp.cpu(), lp4.cpu()))
@@ -404,8 +334,7 @@ def check_relaxed_draw_and_density(lib, N, R, K, scale, tau, exp_space, dtypes=(
             ar = Arena(0)
             dy = ar.put(y)
             out = ar.out(y.numel(), dtype)
-            assert lib.raw("zs_cat_exp" + sfx(dtype), _ptr(dy), _ptr(out), y.numel(), _stream()) == 0
-            torch.cuda.synchronize()
+            assert lib.raw("zs_cat_exp" + sfx(dtype), ptr(dy), ptr(out), y.numel(), stream()) == 0
             ar.check_guards()
             assert same_bits(out, ey), "exp(y) is not the device exp of the y written"
     return found
@@ -467,7 +396,6 @@ def check_log_mass_backward(lib, N, R, K, scale, dtypes=(F32, F64), shifts=(0, 1
             rc2, gl_w, gx_w = c2b(lib, dtype, ar, dl, None, dw, dg, K, R, N, True)
             rc3, gl_w2, gx_w2 = c2b(lib, dtype, ar, dl, None, dw, dg, K, R, N, True)
             assert rc == 0 and rc1 == 0 and rc2 == 0 and rc3 == 0
-            torch.cuda.synchronize()
             ar.check_guards()
             assert same_bits(gl_i, gl_i2) and same_bits(gl_w, gl_w2) and same_bits(gx_w, gx_w2), \
                 "K-summed gradients differ between two calls"
@@ -509,7 +437,6 @@ def check_relaxed_backward(lib, N, R, K, scale, tau, exp_space, dtypes=(F32, F64
             rc3, gy4, gl4 = c4b(lib, dtype, ar, dl, y, tau, exp_space, dg, K, R, N)
             rc4, gy4_b, gl4_b = c4b(lib, dtype, ar, dl, y, tau, exp_space, dg, K, R, N)
             assert rc == 0 and rc1 == 0 and rc2 == 0 and rc3 == 0 and rc4 == 0
-            torch.cuda.synchronize()
             ar.check_guards()
             assert same_bits(gl3, gl3_b) and same_bits(gl4, gl4_b) and same_bits(gy4, gy4_b), \
                 "K-summed gradients differ between two calls"
@@ -580,7 +507,6 @@ def test_out_of_range_index_gives_nan_for_that_draw_only(lib):
             bad_idx[k, r] = v
         rc2, bad = c2(lib, dtype, ar, dl, ar.put(bad_idx), None, K, R, N)
         assert rc == 0 and rc2 == 0
-        torch.cuda.synchronize()
         ar.check_guards()
         good, bad = good.cpu().view(K, R), bad.cpu().view(K, R)
         mask = torch.zeros(K, R, dtype=torch.bool)
@@ -599,8 +525,8 @@ def test_rejected_arguments_write_nothing(lib):
         didx = ar.put(torch.zeros(K, R, dtype=I64))
         # every output any entry point could write, of the full size of the valid problem
         oi, on, on2, ol, og = ar.out(K * R, I64), ar.out(K * R * N, dtype), ar.out(K * R * N, dtype), ar.out(K * R, dtype), ar.out(R * N, dtype)
-        s, st = sfx(dtype), _stream()
-        p = _ptr
+        s, st = sfx(dtype), stream()
+        p = ptr
 
         def every(lgp, k, r, n, tau, relaxed_only=False):
             """the return codes of all entry points (or of the four with a temperature) on these arguments"""
@@ -625,6 +551,5 @@ def test_rejected_arguments_write_nothing(lib):
         assert lib.raw("zs_cat_logprob" + s, p(dl), p(didx), None, K * R + 1, p(ol), K, R, N, st) == EINVAL        # a period that is none
         assert lib.raw("zs_cat_sample_logprob" + s, p(dl), p(du), None, None, None, K, R, N, 0, 0, None, st) == EINVAL   # nothing to write
         torch.cuda.synchronize()
-        for buf, o, n in ar.outs:
-            assert untouched(buf), "a rejected call wrote something"
+        assert ar.untouched(), "a rejected call wrote something"
     assert lib.raw("zs_cat_group_lanes", 0) == 0 and lib.raw("zs_cat_group_lanes", 4) == 1 and lib.raw("zs_cat_group_lanes", 4099) == 64

@@ -17,15 +17,15 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_abi import DEV, EINVAL, Arena, load, sfx, stream
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 LD = np.longdouble
-EINVAL, ENOTSUP = -1, -2
+NAN = float("nan")          # the fill of every arena of this file
 MASK, INTERLEAVE = 0, 1
 NORMAL, LOGISTIC = 0, 1
 NONE, SCALAR, ROWS = 0, 1, 2
-GUARD = 4
 BS = [1, 3, 65, 257]
 DS = [1, 2, 3, 4, 5, 8, 63, 64, 65, 257, 785]
 DS_PAIRS = [2, 4, 6, 130]
@@ -35,45 +35,7 @@ DTYPES = [pytest.param(torch.float32, id="f32"), pytest.param(torch.float64, id=
 
 @pytest.fixture(scope="module")
 def lib():
-    from zhusuan import _flow_hip
-    return _flow_hip.lib(_flow_hip.LIB_PATH)
-
-
-def sfx(dtype):
-    return "_f32" if dtype == torch.float32 else "_f64"
-
-
-def stream():
-    from zhusuan import _hip
-    return _hip.stream_for(torch.empty(0, device=DEV))
-
-
-class Arena(object):
-    """Device operands, each inside its own buffer: GUARD NaN elements, `off` more (0: aligned to 4 elements, 1: not), the
-    data, GUARD NaN elements."""
-
-    def __init__(self, dtype, off):
-        self.dtype, self.off, self.bufs = dtype, off, []
-
-    def _view(self, shape):
-        n = int(np.prod(shape))
-        o = GUARD + self.off
-        buf = torch.full((o + n + GUARD,), float("nan"), dtype=self.dtype, device=DEV)
-        self.bufs.append((buf, o, n))
-        return buf[o:o + n].view(*shape)
-
-    def put(self, arr):
-        v = self._view(arr.shape)
-        v.copy_(torch.from_numpy(np.ascontiguousarray(arr.astype(np.float64))).to(self.dtype))
-        return v
-
-    def out(self, *shape):
-        return self._view(shape)
-
-    def guards_intact(self):
-        torch.cuda.synchronize()
-        for buf, o, n in self.bufs:
-            assert bool(torch.isnan(buf[:o]).all()) and bool(torch.isnan(buf[o + n:]).all()), "write outside the tensor"
+    return load("flow")
 
 
 def rnd(rng, dtype, *shape):
@@ -122,9 +84,9 @@ def check_mask(lib, dtype, B, D, maskkind, rng):
     OM = 1 - M
     for sign in (1.0, -1.0):
         def run(off):
-            A = Arena(dtype, off)
+            A = Arena(shift=off, fill=NAN, dtype=dtype)
             dx, dm, dsh, dg = A.put(x), A.put(mask), A.put(shift), A.put(gy)
-            o_split, o_sbwd, o_y, o_gx, o_gs = (A.out(B, D) for _ in range(5))
+            o_split, o_sbwd, o_y, o_gx, o_gs = (A.out((B, D)) for _ in range(5))
             st = stream()
             assert lib.raw("zs_flow_split" + sfx(dtype), MASK, dx.data_ptr(), dm.data_ptr(), o_split.data_ptr(), B, D, 0, st) == 0
             assert lib.raw("zs_flow_split_bwd" + sfx(dtype), MASK, dg.data_ptr(), dm.data_ptr(), o_sbwd.data_ptr(), B, D, 0, st) == 0
@@ -132,7 +94,7 @@ def check_mask(lib, dtype, B, D, maskkind, rng):
                            o_y.data_ptr(), B, D, 0, st) == 0
             assert lib.raw("zs_flow_merge_bwd" + sfx(dtype), MASK, dg.data_ptr(), dm.data_ptr(), sign, o_gx.data_ptr(),
                            o_gs.data_ptr(), B, D, 0, st) == 0
-            A.guards_intact()
+            A.check_guards()
             within(o_split, M * X, np.abs(M * X), dtype)
             within(o_sbwd, M * G, np.abs(M * G), dtype)
             within(o_y, M * X + (OM * X + sign * SH * OM), np.abs(M * X) + np.abs(OM * X) + np.abs(SH * OM), dtype)
@@ -161,10 +123,10 @@ def check_interleave(lib, dtype, B, D, sel, rng):
     X, G, SH = ld(x), ld(gy), ld(shift)
     for sign in (1.0, -1.0):
         def run(off):
-            A = Arena(dtype, off)
+            A = Arena(shift=off, fill=NAN, dtype=dtype)
             dx, dg, dsh, dgh = A.put(x), A.put(gy), A.put(shift), A.put(gh)
-            o_split, o_gs = A.out(B, H), A.out(B, H)
-            o_sbwd, o_y, o_gx = A.out(B, D), A.out(B, D), A.out(B, D)
+            o_split, o_gs = A.out((B, H)), A.out((B, H))
+            o_sbwd, o_y, o_gx = A.out((B, D)), A.out((B, D)), A.out((B, D))
             st = stream()
             assert lib.raw("zs_flow_split" + sfx(dtype), INTERLEAVE, dx.data_ptr(), None, o_split.data_ptr(), B, D, sel, st) == 0
             assert lib.raw("zs_flow_split_bwd" + sfx(dtype), INTERLEAVE, dgh.data_ptr(), None, o_sbwd.data_ptr(), B, D, sel, st) == 0
@@ -172,7 +134,7 @@ def check_interleave(lib, dtype, B, D, sel, rng):
                            B, D, sel, st) == 0
             assert lib.raw("zs_flow_merge_bwd" + sfx(dtype), INTERLEAVE, dg.data_ptr(), None, sign, o_gx.data_ptr(),
                            o_gs.data_ptr(), B, D, sel, st) == 0
-            A.guards_intact()
+            A.check_guards()
             assert torch.equal(o_split, dx[:, sel::2])                                  # copies are exact
             assert torch.equal(o_sbwd[:, sel::2], dgh) and bool((o_sbwd[:, on::2] == 0).all())
             assert torch.equal(o_y[:, sel::2], dx[:, sel::2])
@@ -202,9 +164,9 @@ def check_scale(lib, dtype, B, D, rng):
         Y = X * F
 
         def run(off):
-            A = Arena(dtype, off)
+            A = Arena(shift=off, fill=NAN, dtype=dtype)
             dx, dg, dls, dgl = A.put(x), A.put(gy), A.put(ls), A.put(gld)
-            o_y, o_ld, o_gx, o_gls, o_gls0 = A.out(B, D), A.out(1), A.out(B, D), A.out(D), A.out(D)
+            o_y, o_ld, o_gx, o_gls, o_gls0 = A.out((B, D)), A.out(1), A.out((B, D)), A.out(D), A.out(D)
             inplace = A.put(x)
             o_ld2, o_gls2 = A.out(1), A.out(D)
             st = stream()
@@ -216,7 +178,7 @@ def check_scale(lib, dtype, B, D, rng):
             assert lib.raw(name, *args, dgl.data_ptr(), sign, o_gx.data_ptr(), o_gls.data_ptr(), B, D, st) == 0
             assert lib.raw(name, *args, dgl.data_ptr(), sign, o_gx.data_ptr(), o_gls2.data_ptr(), B, D, st) == 0
             assert lib.raw(name, *args, None, sign, o_gx.data_ptr(), o_gls0.data_ptr(), B, D, st) == 0
-            A.guards_intact()
+            A.check_guards()
             within(o_y, Y, np.abs(Y), dtype)
             assert torch.equal(inplace, o_y), "in place differs from out of place"
             within(o_ld, LS.sum(), np.abs(LS).sum(), dtype, n=D)
@@ -250,10 +212,10 @@ def check_made(lib, dtype, B, D, rng):
     col = D // 2
 
     def run(off):
-        A = Arena(dtype, off)
+        A = Arena(shift=off, fill=NAN, dtype=dtype)
         dx, dgu, dgl, dnet = A.put(x), A.put(gu), A.put(gld), A.put(net)
-        o_u, o_ld, o_gx, o_gx2, o_inv = (A.out(B, D) for _ in range(5))
-        o_gnet, o_gnet2 = A.out(B, 2 * D), A.out(B, 2 * D)
+        o_u, o_ld, o_gx, o_gx2, o_inv = (A.out((B, D)) for _ in range(5))
+        o_gnet, o_gnet2 = A.out((B, 2 * D)), A.out((B, 2 * D))
         o_inv.fill_(7.0)
         st = stream()
         assert lib.raw("zs_flow_made_fwd" + sfx(dtype), dx.data_ptr(), dnet.data_ptr(), o_u.data_ptr(), o_ld.data_ptr(), B, D, st) == 0
@@ -262,7 +224,7 @@ def check_made(lib, dtype, B, D, rng):
         assert lib.raw("zs_flow_made_bwd" + sfx(dtype), dgu.data_ptr(), None, dx.data_ptr(), dnet.data_ptr(),
                        o_gx2.data_ptr(), o_gnet2.data_ptr(), B, D, st) == 0
         assert lib.raw("zs_flow_made_inv_col" + sfx(dtype), dgu.data_ptr(), dnet.data_ptr(), o_inv.data_ptr(), B, D, col, st) == 0
-        A.guards_intact()
+        A.check_guards()
         within(o_u, U, Su, dtype)
         assert torch.equal(o_ld, -dnet[:, D:])
         within(o_gx, GU * E, np.abs(GU * E), dtype)
@@ -313,10 +275,10 @@ def check_tail(lib, dtype, B, D, base, rng):
         lp, S, dz = base_truth(base, Z, LOC, SC)
 
         def run(off):
-            A = Arena(dtype, off)
+            A = Arena(shift=off, fill=NAN, dtype=dtype)
             dz_, dg, dloc, dsc, dlds, dldr = A.put(z), A.put(g), A.put(loc), A.put(scale), A.put(lds), A.put(ldr)
             o_n, o_s, o_r, o_r2, o_gl = (A.out(B) for _ in range(5))
-            o_gz, o_gz2 = A.out(B, D), A.out(B, D)
+            o_gz, o_gz2 = A.out((B, D)), A.out((B, D))
             st = stream()
             name = "zs_flow_tail" + sfx(dtype)
             head = (base, dz_.data_ptr(), dloc.data_ptr(), dsc.data_ptr(), param_rows)
@@ -328,7 +290,7 @@ def check_tail(lib, dtype, B, D, base, rng):
             head = (base, dg.data_ptr(), dz_.data_ptr(), dloc.data_ptr(), dsc.data_ptr(), param_rows)
             assert lib.raw(name, *head, o_gz.data_ptr(), o_gl.data_ptr(), B, D, st) == 0
             assert lib.raw(name, *head, o_gz2.data_ptr(), None, B, D, st) == 0
-            A.guards_intact()
+            A.check_guards()
             within(o_n, lp.sum(1), S.sum(1), dtype, n=D)
             within(o_s, lp.sum(1) + ld(lds)[0], S.sum(1) + abs(ld(lds)[0]), dtype, n=D + 1)
             within(o_r, lp.sum(1) + ld(ldr), S.sum(1) + np.abs(ld(ldr)), dtype, n=D + 1)

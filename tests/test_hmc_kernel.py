@@ -12,35 +12,17 @@ import pytest
 import torch
 
 import hmc_host
+from kernel_abi import DEV, EINVAL, ENOTSUP, F32, F64, SENTINEL, Arena, load, ptr, sfx, stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 BEGIN, STEP, END = 0, 1, 2
-EINVAL, ENOTSUP = -1, -2
-GUARD = 4
-SENTINEL = 777.0
 EPS = 0.37
-F32, F64 = torch.float32, torch.float64
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from zhusuan import _hmc_hip
-    return _hmc_hip.lib(_hmc_hip.LIB_PATH)
-
-
-def _ptr(t):
-    return None if t is None else (t if isinstance(t, int) else t.data_ptr())
-
-
-def _stream():
-    from zhusuan import _hip
-    return _hip.stream_for(torch.empty(0, device=DEV))
-
-
-def sfx(dtype):
-    return "_f32" if dtype == F32 else "_f64"
+    return load("hmc")
 
 
 def state_block(eps=EPS, **kw):
@@ -56,10 +38,10 @@ def raw_move(lib, dtype, kind, rows, n, C, state, ksum, seed=0, call=0, rs=None,
     table = (_hmc_hip.HmcTensor * max(len(rows), 1))()
     for e, r in zip(table, rows):
         for k in ("q0", "q", "p", "grad", "z", "p0", "q_out"):
-            setattr(e, k, _ptr(r.get(k)))
+            setattr(e, k, ptr(r.get(k)))
         e.start, e.row = r["start"], r["row"]
     return lib.raw("zs_hmc_move" + sfx(dtype), kind, table if rows else None, len(rows) if n_tensors is None else n_tensors, n, C,
-                   _ptr(state), _ptr(ksum), seed, call, _ptr(rs), _stream())
+                   ptr(state), ptr(ksum), seed, call, ptr(rs), stream())
 
 
 def raw_select(lib, dtype, rows, n, C, accept, n_tensors=None):
@@ -67,10 +49,10 @@ def raw_select(lib, dtype, rows, n, C, accept, n_tensors=None):
     table = (_hmc_hip.HmcTensor * max(len(rows), 1))()
     for e, r in zip(table, rows):
         for k in ("q0", "q", "q_out"):
-            setattr(e, k, _ptr(r.get(k)))
+            setattr(e, k, ptr(r.get(k)))
         e.start, e.row = r["start"], r["row"]
     return lib.raw("zs_hmc_select" + sfx(dtype), table if rows else None, len(rows) if n_tensors is None else n_tensors, n, C,
-                   _ptr(accept), _stream())
+                   ptr(accept), stream())
 
 
 def raw_decide(lib, dtype, chunks, C, logp0, logp1, u, state, out, accept, adapting=0, delta=0.8, gamma=0.05, t0=100., kappa=0.75,
@@ -78,29 +60,15 @@ def raw_decide(lib, dtype, chunks, C, logp0, logp1, u, state, out, accept, adapt
     from zhusuan import _hmc_hip
     table = (_hmc_hip.HmcChunk * max(len(chunks), 1))()
     for e, (k0, k1, slots, f64) in zip(table, chunks):
-        e.k0, e.k1, e.slots, e.is_f64 = _ptr(k0), _ptr(k1), slots, f64
+        e.k0, e.k1, e.slots, e.is_f64 = ptr(k0), ptr(k1), slots, f64
     return lib.raw("zs_hmc_decide" + sfx(dtype), table if chunks else None, len(chunks) if n_chunks is None else n_chunks, C,
-                   _ptr(logp0), _ptr(logp1), _ptr(u), _ptr(state), _ptr(out), _ptr(accept), adapting, delta, gamma, t0, kappa,
-                   seed, call, _ptr(rs), _stream())
+                   ptr(logp0), ptr(logp1), ptr(u), ptr(state), ptr(out), ptr(accept), adapting, delta, gamma, t0, kappa,
+                   seed, call, ptr(rs), stream())
 
 
-def place(flat, sizes, shift):
-    """Device copies of the pieces of `flat`, each inside its own buffer with GUARD sentinel elements on both sides and
-    `shift` more in front; returns (views, buffers)."""
-    views, bufs, a = [], [], 0
-    for k in sizes:
-        o = GUARD + shift
-        buf = torch.full((o + k + GUARD,), SENTINEL, dtype=flat.dtype, device=DEV)
-        buf[o:o + k] = flat[a:a + k].to(DEV)
-        views.append(buf[o:o + k])
-        bufs.append((buf, o, k))
-        a += k
-    return views, bufs
-
-
-def guards_intact(bufs):
-    for buf, o, k in bufs:
-        assert bool((buf[:o] == SENTINEL).all()) and bool((buf[o + k:] == SENTINEL).all()), "write outside the tensor"
+def place(ar, flat, sizes):
+    """Device copies of the pieces of `flat`, each inside a guarded buffer of its own in the arena `ar`; returns the views."""
+    return [ar.put(piece) for piece in torch.split(flat, sizes)]
 
 
 def cat(views):
@@ -121,20 +89,19 @@ def run_move(lib, dtype, kind, C, rows, shift, data, inject=True, seed=5, call=9
     n = starts[-1]
     slots = sum(hmc_host.pieces(r) for r in rows)
     zero = torch.zeros_like(q)
-    vq0, bq0 = place(q, sizes, shift)
-    vq, bq = place(zero if kind == BEGIN else q, sizes, shift)
-    vp, bp = place(zero if kind == BEGIN else p, sizes, shift)
-    vg, bg = place(g, sizes, shift)
-    vz, bz = place(z, sizes, shift)
-    vp0, bp0 = place(zero, sizes, shift)
-    ks, bk = place(torch.full((C * slots,), float("nan"), dtype=dtype), [C * slots], shift)
+    ar = Arena(shift)
+    vq0 = place(ar, q, sizes)
+    vq = place(ar, zero if kind == BEGIN else q, sizes)
+    vp = place(ar, zero if kind == BEGIN else p, sizes)
+    vg = place(ar, g, sizes)
+    vz = place(ar, z, sizes)
+    vp0 = place(ar, zero, sizes)
+    ks = place(ar, torch.full((C * slots,), float("nan"), dtype=dtype), [C * slots])
     table = [dict(q0=vq0[i], q=vq[i], p=vp[i], grad=vg[i], z=vz[i] if inject else None, p0=vp0[i], start=starts[i], row=rows[i])
              for i in range(len(rows))]
     rc = raw_move(lib, dtype, kind, table, n, C, state_block(eps), ks[0], seed=seed, call=call, rs=rs)
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    for b in (bq0, bq, bp, bg, bz, bp0, bk):
-        guards_intact(b)
+    ar.check_guards()
     assert torch.equal(cat(vq0), q) and torch.equal(cat(vg), g) and torch.equal(cat(vz), z), "an input was modified"
     ksum = ks[0].cpu().view(C, slots)
     if kind == STEP:
@@ -244,7 +211,7 @@ def test_an_offset_view_among_aligned_tensors(lib):
     starts = [0, sizes[0], sizes[0] + sizes[1]]
     ops = {}
     for name, flat in (("q0", q), ("q", torch.zeros_like(q)), ("p", torch.zeros_like(q)), ("grad", g), ("z", z), ("p0", torch.zeros_like(q))):
-        ops[name] = [place(flat[s:s + k], [k], 1 if i == 1 and name in ("q", "grad") else 0)[0][0] for i, (s, k) in enumerate(zip(starts, sizes))]
+        ops[name] = [Arena(1 if i == 1 and name in ("q", "grad") else 0).put(flat[s:s + k]) for i, (s, k) in enumerate(zip(starts, sizes))]
     slots = sum(hmc_host.pieces(r) for r in rows)
     ks = torch.full((C * slots,), float("nan"), device=DEV)
     table = [dict(dict((k, v[i]) for k, v in ops.items()), start=starts[i], row=rows[i]) for i in range(3)]
@@ -258,7 +225,7 @@ def philox(name, n, seed, call, rs=None):
     """Elements [0, n) of the MAIN library's stream."""
     from zhusuan import _hip
     out = torch.empty(n, dtype=F32, device=DEV)
-    _hip.lib().call(name, out.data_ptr(), n, seed, call, _ptr(rs), _hip.stream_for(out))
+    _hip.lib().call(name, out.data_ptr(), n, seed, call, ptr(rs), _hip.stream_for(out))
     torch.cuda.synchronize()
     return out.cpu()
 
@@ -318,15 +285,13 @@ def run_decide(lib, dtype, C, k, l0, l1, u, state, adapting=0, seed=0, call=0, r
     d = [t.to(DEV) for t in k]
     L0, L1 = l0.to(dtype).to(DEV), l1.to(dtype).to(DEV)
     U = None if u is None else u.to(dtype).to(DEV)
-    out = torch.full((5 * C + 2 * GUARD,), SENTINEL, dtype=F64, device=DEV)
-    acc = torch.full((C + 2 * GUARD,), 777, dtype=torch.int32, device=DEV)
-    rc = raw_decide(lib, dtype, [(d[0], d[1], 3, 0), (d[2], d[3], 2, 1)], C, L0, L1, U, state, out[GUARD:], acc[GUARD:],
+    ar = Arena()
+    out, acc = ar.out((5, C), F64), ar.out(C, torch.int32)
+    rc = raw_decide(lib, dtype, [(d[0], d[1], 3, 0), (d[2], d[3], 2, 1)], C, L0, L1, U, state, out, acc,
                     adapting=adapting, seed=seed, call=call, rs=rs)
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    assert bool((out[:GUARD] == SENTINEL).all()) and bool((out[GUARD + 5 * C:] == SENTINEL).all())
-    assert bool((acc[:GUARD] == 777).all()) and bool((acc[GUARD + C:] == 777).all())
-    return out[GUARD:GUARD + 5 * C].cpu().view(5, C), acc[GUARD:GUARD + C].cpu(), state.cpu()
+    ar.check_guards()
+    return out.cpu(), acc.cpu(), state.cpu()
 
 
 def close40(got, want, scale=None):
@@ -424,14 +389,11 @@ def test_select_is_exactly_where(lib, C, rows, dtype):
     want = torch.cat([torch.where(accept.bool().view(C, 1), q[s:s + k].view(C, -1), q0[s:s + k].view(C, -1)).reshape(-1)
                       for s, k in zip(starts, sizes)])
     for shift in (0, 1):
-        v0, b0 = place(q0, sizes, shift)
-        v1, b1 = place(q, sizes, shift)
-        vo, bo = place(torch.zeros_like(q), sizes, shift)
+        ar = Arena(shift)
+        v0, v1, vo = place(ar, q0, sizes), place(ar, q, sizes), place(ar, torch.zeros_like(q), sizes)
         table = [dict(q0=v0[i], q=v1[i], q_out=vo[i], start=starts[i], row=rows[i]) for i in range(len(rows))]
         assert raw_select(lib, dtype, table, n, C, accept.to(DEV)) == 0
-        torch.cuda.synchronize()
-        for b in (b0, b1, bo):
-            guards_intact(b)
+        ar.check_guards()
         assert torch.equal(cat(vo), want) and torch.equal(cat(v0), q0) and torch.equal(cat(v1), q)
         # in place: q_out = q0
         table = [dict(q0=v0[i], q=v1[i], q_out=v0[i], start=starts[i], row=rows[i]) for i in range(len(rows))]

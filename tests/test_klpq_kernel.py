@@ -25,15 +25,11 @@ import pytest
 import torch
 
 import klpq_host
+from kernel_abi import EINVAL, ENOTSUP, F32, F64, Arena, load, ptr, same_bits, sfx, stream, unit, untouched
 
 gpu = pytest.mark.gpu
 
-DEV = "cuda:0"
-EINVAL, ENOTSUP = -1, -2
 MODEL_GRAD, BOUND_ONLY, GCOST_MEAN = 1, 2, 4
-GUARD = 4
-SENTINEL = 777.0
-F32, F64 = torch.float32, torch.float64
 KS = [1, 2, 3, 5, 31, 32, 33, 50, 63, 64, 65, 130, 257]
 BS = [1, 3, 65, 257]
 MAX_TERMS = 8
@@ -93,10 +89,6 @@ def storage(layout, side, i, n, flipped):
 
 
 # ------------------------------------------------------------------------------------------------ the bounds
-def unit(dtype):
-    return 2.0 ** -24 if dtype == F32 else 2.0 ** -53
-
-
 def tiny(dtype):
     return 2.0 ** -126 if dtype == F32 else 2.0 ** -1022
 
@@ -252,55 +244,7 @@ def test_float32_torch_composition_stays_inside_the_bounds(K):
 # ------------------------------------------------------------------------------------------------ device plumbing
 @pytest.fixture(scope="module")
 def lib():
-    from zhusuan import _klpq_hip
-    return _klpq_hip.lib(_klpq_hip.LIB_PATH)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    from zhusuan import _hip
-    return _hip.stream_for(torch.empty(0, device=DEV))
-
-
-def sfx(dtype):
-    return "_f32" if dtype == F32 else "_f64"
-
-
-class Arena(object):
-    """Device operands inside guarded buffers: GUARD sentinels on both sides, `shift` more elements in front."""
-
-    def __init__(self, shift):
-        self.shift = shift
-        self.outs = []
-
-    def _buf(self, n, dtype):
-        o = GUARD + self.shift
-        return torch.full((o + n + GUARD,), SENTINEL, dtype=dtype, device=DEV), o
-
-    def put(self, t, dtype):
-        if t is None:
-            return None
-        buf, o = self._buf(t.numel(), dtype)
-        buf[o:o + t.numel()] = t.reshape(-1).to(dtype).to(DEV)
-        return buf[o:o + t.numel()]
-
-    def out(self, n, dtype):
-        buf, o = self._buf(n, dtype)
-        self.outs.append((buf, o, n))
-        return buf[o:o + n]
-
-    def check_guards(self):
-        for buf, o, n in self.outs:
-            assert bool((buf[:o] == SENTINEL).all()) and bool((buf[o + n:] == SENTINEL).all()), "write outside the tensor"
-
-
-def same_bits(a, b):
-    a, b = a.cpu().contiguous(), b.cpu().contiguous()
-    it = torch.int32 if a.dtype == F32 else torch.int64
-    return a.shape == b.shape and torch.equal(a.view(it), b.view(it))
+    return load("klpq")
 
 
 def term_row(row, t, val, store, ar, dtype, want_grad):
@@ -311,7 +255,7 @@ def term_row(row, t, val, store, ar, dtype, want_grad):
     row.value = val.data_ptr()
     row.sk, row.sb = (0 if k == 1 else sk), (0 if b == 1 else sb)
     grad = ar.out(k * b, dtype) if want_grad else None
-    row.grad = _ptr(grad)
+    row.grad = ptr(grad)
 
     def logical(g):
         g = g.cpu()
@@ -327,7 +271,7 @@ def run_case(lib, dtype, d, K, B, layout, shift, flipped):
     terms = {"p": d["p"], "q": d["q"]}
     if flipped:          # every term in the opposite layout, shared terms spelled out
         terms = {s: [t.expand(K, B) for t in ts] for s, ts in terms.items()}
-    st = _stream()
+    st = stream()
     gcost, gbound, gmean = ar.put(d["gcost"], dtype), ar.put(d["gbound"], dtype), ar.put(d["gmean"], dtype)
     with_mean = B <= MEAN_MAX_B
 
@@ -355,18 +299,18 @@ def run_case(lib, dtype, d, K, B, layout, shift, flipped):
         tabs, _ = tables(False)
         w, cost, bound, ess = ar.out(B * K, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(B, dtype)
         mean = ar.out(1, dtype) if with_mean else None
-        rc = lib.raw("zs_klpq_forward" + sfx(dtype), tabs["p"], Tp, tabs["q"], Tq, K, B, 0, _ptr(w), _ptr(cost), _ptr(bound), _ptr(ess),
-                     _ptr(mean), st)
+        rc = lib.raw("zs_klpq_forward" + sfx(dtype), tabs["p"], Tp, tabs["q"], Tq, K, B, 0, ptr(w), ptr(cost), ptr(bound), ptr(ess),
+                     ptr(mean), st)
         assert rc == 0
         cost_mg, bound2, ess2 = ar.out(B, dtype), ar.out(B, dtype), ar.out(B, dtype)
-        rc = lib.raw("zs_klpq_forward" + sfx(dtype), tabs["p"], Tp, tabs["q"], Tq, K, B, MODEL_GRAD, None, _ptr(cost_mg), _ptr(bound2),
-                     _ptr(ess2), None, st)
+        rc = lib.raw("zs_klpq_forward" + sfx(dtype), tabs["p"], Tp, tabs["q"], Tq, K, B, MODEL_GRAD, None, ptr(cost_mg), ptr(bound2),
+                     ptr(ess2), None, st)
         assert rc == 0
         tabA, gA = tables(False)
-        rc = lib.raw("zs_klpq_backward" + sfx(dtype), tabA["p"], Tp, tabA["q"], Tq, K, B, 0, _ptr(w), _ptr(gcost), _ptr(gbound), st)
+        rc = lib.raw("zs_klpq_backward" + sfx(dtype), tabA["p"], Tp, tabA["q"], Tq, K, B, 0, ptr(w), ptr(gcost), ptr(gbound), st)
         assert rc == 0
         tabB, gB = tables(True)          # (the first variational term hands in a NULL gradient pointer)
-        rc = lib.raw("zs_klpq_backward" + sfx(dtype), tabB["p"], Tp, tabB["q"], Tq, K, B, MODEL_GRAD | GCOST_MEAN, _ptr(w), _ptr(gmean),
+        rc = lib.raw("zs_klpq_backward" + sfx(dtype), tabB["p"], Tp, tabB["q"], Tq, K, B, MODEL_GRAD | GCOST_MEAN, ptr(w), ptr(gmean),
                      None, st)
         assert rc == 0
         torch.cuda.synchronize()
@@ -428,8 +372,7 @@ def test_a_row_of_all_minus_infinity_gives_nan_there_and_leaves_its_neighbours_a
             ar = Arena(0)
             tabs, keep = simple_tables(ar, dtype, case, K, B)
             o = [ar.out(B * K, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(1, dtype)]
-            assert lib.raw("zs_klpq_forward" + sfx(dtype), tabs["p"], 2, tabs["q"], 1, K, B, 0, *[_ptr(t) for t in o], _stream()) == 0
-            torch.cuda.synchronize()
+            assert lib.raw("zs_klpq_forward" + sfx(dtype), tabs["p"], 2, tabs["q"], 1, K, B, 0, *[ptr(t) for t in o], stream()) == 0
             ar.check_guards()
             outs.append([o[0].cpu().view(B, K)] + [t.cpu() for t in o[1:]])
         good, hit = outs
@@ -447,28 +390,27 @@ def test_bound_only_and_null_outputs(lib):
     for dtype in (F32, F64):
         ar = Arena(0)
         tabs, keep = simple_tables(ar, dtype, d, K, B)
-        name, st = "zs_klpq_forward" + sfx(dtype), _stream()
+        name, st = "zs_klpq_forward" + sfx(dtype), stream()
         full = [ar.out(B * K, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(1, dtype)]
-        assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, 0, *[_ptr(t) for t in full], st) == 0
+        assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, 0, *[ptr(t) for t in full], st) == 0
         # bound_only writes only bound, whatever else is handed in
         only = [ar.out(B * K, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(1, dtype)]
-        assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, BOUND_ONLY, *[_ptr(t) for t in only], st) == 0
+        assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, BOUND_ONLY, *[ptr(t) for t in only], st) == 0
         alone = ar.out(B, dtype)
-        assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, BOUND_ONLY, None, None, _ptr(alone), None, None, st) == 0
-        assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, BOUND_ONLY, _ptr(only[0]), None, None, None, None, st) == EINVAL
+        assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, BOUND_ONLY, None, None, ptr(alone), None, None, st) == 0
+        assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, BOUND_ONLY, ptr(only[0]), None, None, None, None, st) == EINVAL
         # each output alone: the others NULL
         singles = []
         for i in range(5):
             o = ar.out(full[i].numel(), dtype)
             args = [None] * 5
-            args[i] = _ptr(o)
+            args[i] = ptr(o)
             assert lib.raw(name, tabs["p"], 3, tabs["q"], 2, K, B, 0, *args, st) == 0
             singles.append(o)
-        torch.cuda.synchronize()
         ar.check_guards()
         assert same_bits(only[2], full[2]) and same_bits(alone, full[2])
         for i in (0, 1, 3, 4):
-            assert bool((only[i] == SENTINEL).all()), "bound_only wrote something besides bound"
+            assert untouched(only[i]), "bound_only wrote something besides bound"
         for a, b in zip(singles, full):
             assert same_bits(a, b), "an output alone differs from the same output among the others"
 
@@ -493,13 +435,13 @@ def test_rejected_arguments_write_nothing(lib):
             nograd[i].grad = None
         o = [ar.out(B * K, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(B, dtype), ar.out(1, dtype)]
         w, gc = ar.put(torch.full((B, K), 0.2, dtype=F64), dtype), ar.put(d["gcost"], dtype)
-        po, st, s = [_ptr(t) for t in o], _stream(), sfx(dtype)
+        po, st, s = [ptr(t) for t in o], stream(), sfx(dtype)
 
         def fwd(p, tp, q, tq, k, b, flags=0, outs=po):
             return lib.raw("zs_klpq_forward" + s, p, tp, q, tq, k, b, flags, *outs, st)
 
         def bwd(p, tp, q, tq, k, b, w_=w, gc_=gc):
-            return lib.raw("zs_klpq_backward" + s, p, tp, q, tq, k, b, 0, _ptr(w_), _ptr(gc_), None, st)
+            return lib.raw("zs_klpq_backward" + s, p, tp, q, tq, k, b, 0, ptr(w_), ptr(gc_), None, st)
         P, Q = tabs["p"], tabs["q"]
         for f in (fwd, bwd):
             assert f(P, 0, Q, 2, K, B) == EINVAL and f(P, 2, Q, 0, K, B) == EINVAL and f(P, -1, Q, 2, K, B) == EINVAL
@@ -513,7 +455,6 @@ def test_rejected_arguments_write_nothing(lib):
         assert bwd(P, 2, Q, 2, K, B, w_=None) == EINVAL and bwd(P, 2, Q, 2, K, B, gc_=None) == EINVAL
         assert bwd(nograd, 2, nograd, 2, K, B) == EINVAL                           # no gradient asked for
         torch.cuda.synchronize()
-        for buf, off, n in ar.outs:
-            assert bool((buf == SENTINEL).all()), "a rejected call wrote something"
+        assert ar.untouched(), "a rejected call wrote something"
     assert lib.raw("zs_klpq_max_terms") == MAX_TERMS and lib.raw("zs_klpq_mean_max_batch") == MEAN_MAX_B
     assert [lib.raw("zs_klpq_group_lanes", n) for n in (0, 1, 2, 3, 5, 33, 64, 65, 257)] == [0, 1, 2, 4, 8, 64, 64, 64, 64]

@@ -11,41 +11,33 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_abi import DEV, EINVAL, ENOTSUP, SENTINEL, Arena, load, ptr, stream
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 HYPER = dict(lr=1e-2, decay=0.9, epsilon=1e-3, alpha=0.3, beta=0.02)
 SGLD, PSGLD, PRE, POST = 0, 1, 2, 3
 SECOND, RESAMPLE = 1, 2
 # (kind, flags) of every form of the update
 FORMS = [(SGLD, 0), (PSGLD, 0), (PRE, RESAMPLE), (PRE, SECOND), (PRE, SECOND | RESAMPLE), (POST, 0), (POST, SECOND)]
-EINVAL, ENOTSUP = -1, -2
-GUARD = 4          # untouched elements kept on both sides of every operand
-SENTINEL = 777.0
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from zhusuan import _mcmc_hip
-    return _mcmc_hip.lib(_mcmc_hip.LIB_PATH)
-
-
-def _ptr(t):
-    return None if t is None else (t if isinstance(t, int) else t.data_ptr())
+    return load("mcmc")
 
 
 def raw(lib, dtype, kind, rows, n, flags=0, seed=0, call=0, rs=None, hyper=None, n_tensors=None):
     """rows: (q_in, q_out, grad, state, z, start) per tensor (tensors, None, or raw addresses); returns the entry point's code."""
-    from zhusuan import _mcmc_hip, _hip
+    from zhusuan import _mcmc_hip
     h = dict(HYPER, **(hyper or {}))
     table = (_mcmc_hip.McmcTensor * max(len(rows), 1))()
     for e, r in zip(table, rows):
-        e.q_in, e.q_out, e.grad, e.state, e.z = [_ptr(t) for t in r[:5]]
+        e.q_in, e.q_out, e.grad, e.state, e.z = [ptr(t) for t in r[:5]]
         e.start = r[5]
     name = "zs_mcmc_update_f32" if dtype == torch.float32 else "zs_mcmc_update_f64"
-    stream = _hip.stream_for(torch.empty(0, device=DEV))
     return lib.raw(name, kind, table if rows else None, len(rows) if n_tensors is None else n_tensors, n, h["lr"], h["decay"],
-                   h["epsilon"], h["alpha"], h["beta"], flags, seed, call, _ptr(rs), stream)
+                   h["epsilon"], h["alpha"], h["beta"], flags, seed, call, ptr(rs), stream())
 
 
 def truth(kind, flags, q, g, s, z, h=HYPER):
@@ -100,41 +92,22 @@ def state_for(kind, s):
     return a
 
 
-def place(flat, sizes, offsets=None):
-    """Device copies of the pieces of `flat`, each inside its own buffer with GUARD sentinel elements on both sides
-    (offsets[i] extra leading elements shift piece i off its alignment); returns (views, buffers)."""
-    views, bufs, a = [], [], 0
-    for i, k in enumerate(sizes):
-        o = GUARD + (offsets[i] if offsets else 0)
-        buf = torch.full((o + k + GUARD,), SENTINEL, dtype=flat.dtype, device=DEV)
-        buf[o:o + k] = flat[a:a + k].to(DEV)
-        views.append(buf[o:o + k])
-        bufs.append((buf, o, k))
-        a += k
-    return views, bufs
-
-
-def guards_intact(bufs):
-    for buf, o, k in bufs:
-        assert bool((buf[:o] == SENTINEL).all()) and bool((buf[o + k:] == SENTINEL).all()), "write outside the tensor"
-
-
 def run_layout(lib, dtype, kind, flags, sizes, offsets, data, inject, seed=5, call=9, rs=None):
-    """The update on tensors laid out as (sizes, offsets); returns flat (q', s') on the host."""
+    """The update on tensors laid out as (sizes, offsets): every piece of every operand inside a guarded buffer of its own,
+    offsets[i] extra leading elements shifting the pieces of tensor i off their alignment; returns flat (q', s') on the host."""
     q, g, s, z = data
     starts = [int(x) for x in np.cumsum([0] + list(sizes))]
-    qi, bq = place(q, sizes, offsets)
-    qo, bo = place(torch.zeros_like(q), sizes, offsets)
-    gg, bg = place(g, sizes, offsets)
-    ss, bs = place(s, sizes, offsets)
-    zz, bz = place(z, sizes, offsets)
+    arenas = [Arena(shift) for shift in (offsets or [0] * len(sizes))]          # one per tensor: the shift is the arena's
+
+    def place(flat):
+        return [ar.put(piece) for ar, piece in zip(arenas, torch.split(flat, sizes))]
+    qi, qo, gg, ss, zz = [place(t) for t in (q, torch.zeros_like(q), g, s, z)]
     rows = [(qi[i], qo[i], gg[i], ss[i], zz[i] if inject else None, starts[i]) for i in range(len(sizes))]
     rc = raw(lib, dtype, kind, rows, starts[-1], flags=flags, seed=seed, call=call, rs=rs)
     assert rc == 0, rc
-    torch.cuda.synchronize()
-    for b in (bq, bo, bg, bs, bz):
-        guards_intact(b)
-    for a, b in zip(qi, place(q, sizes, offsets)[0]):
+    for ar in arenas:
+        ar.check_guards()
+    for a, b in zip(qi, place(q)):
         assert torch.equal(a, b), "q_in was modified"
     return torch.cat([t.cpu() for t in qo]), torch.cat([t.cpu() for t in ss])
 
@@ -143,7 +116,7 @@ def philox(n, seed, call, rs=None):
     """Elements [0, n) of the MAIN library's zs_philox_normal_f32 stream."""
     from zhusuan import _hip
     out = torch.empty(n, dtype=torch.float32, device=DEV)
-    _hip.lib().call("zs_philox_normal_f32", out.data_ptr(), n, seed, call, _ptr(rs), _hip.stream_for(out))
+    _hip.lib().call("zs_philox_normal_f32", out.data_ptr(), n, seed, call, ptr(rs), _hip.stream_for(out))
     torch.cuda.synchronize()
     return out.cpu()
 

@@ -18,14 +18,10 @@ import pytest
 import torch
 
 import mvn_host
+from kernel_abi import DEV, EINVAL, ENOTSUP, F32, F64, I64, Arena, load, load_main, ptr, same_bits, sfx, stream, unit
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-EINVAL, ENOTSUP = -1, -2
-GUARD = 4
-SENTINEL = 777.0
-F32, F64, I64 = torch.float32, torch.float64, torch.int64
 DS = [1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 31, 32, 33, 63, 64]
 RS = [1, 3, 65]
 KS = [1, 2, 5]
@@ -58,65 +54,12 @@ def grid(D):
 # ------------------------------------------------------------------------------------------------ device plumbing
 @pytest.fixture(scope="module")
 def lib():
-    from zhusuan import _mvn_hip
-    return _mvn_hip.lib(_mvn_hip.LIB_PATH)
+    return load("mvn")
 
 
 @pytest.fixture(scope="module")
 def main_lib():
-    from zhusuan import _hip
-    return _hip.KernelLibrary(_hip.LIB_PATH)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    from zhusuan import _hip
-    return _hip.stream_for(torch.empty(0, device=DEV))
-
-
-def sfx(dtype):
-    return "_f32" if dtype == F32 else "_f64"
-
-
-def unit(dtype):
-    return 2.0 ** -24 if dtype == F32 else 2.0 ** -53
-
-
-class Arena(object):
-    """Device operands inside guarded buffers: GUARD sentinels on both sides, `shift` more elements in front."""
-
-    def __init__(self, shift):
-        self.shift = shift
-        self.outs = []
-
-    def _buf(self, n, dtype):
-        o = GUARD + self.shift
-        return torch.full((o + n + GUARD,), SENTINEL, dtype=dtype, device=DEV), o
-
-    def put(self, t, dtype):
-        if t is None:
-            return None
-        buf, o = self._buf(t.numel(), dtype)
-        buf[o:o + t.numel()] = t.reshape(-1).to(dtype).to(DEV)
-        return buf[o:o + t.numel()]
-
-    def out(self, n, dtype):
-        buf, o = self._buf(n, dtype)
-        self.outs.append((buf, o, n))
-        return buf[o:o + n]
-
-    def check_guards(self):
-        for buf, o, n in self.outs:
-            assert bool((buf[:o] == SENTINEL).all()) and bool((buf[o + n:] == SENTINEL).all()), "write outside the tensor"
-
-
-def same_bits(a, b):
-    a, b = a.cpu(), b.cpu()
-    it = torch.int32 if a.dtype == F32 else torch.int64
-    return torch.equal(a.view(it), b.view(it))
+    return load_main()
 
 
 def assert_close(name, got, truth, tol):
@@ -135,28 +78,28 @@ def assert_close(name, got, truth, tol):
 # ------------------------------------------------------------------------------------------------ raw calls
 def v1(lib, dtype, ar, mean, tril, eps, K, R, D, seed=0, call=0, rs=None):
     z, lp = ar.out(K * R * D, dtype), ar.out(K * R, dtype)
-    rc = lib.raw("zs_mvn_sample_logprob" + sfx(dtype), _ptr(mean), _ptr(tril), _ptr(eps), _ptr(z), _ptr(lp), K, R, D, seed, call,
-                 _ptr(rs), _stream())
+    rc = lib.raw("zs_mvn_sample_logprob" + sfx(dtype), ptr(mean), ptr(tril), ptr(eps), ptr(z), ptr(lp), K, R, D, seed, call,
+                 ptr(rs), stream())
     return rc, z, lp
 
 
 def v1b(lib, dtype, ar, tril, eps, gz, glp, reparam, K, R, D, seed=0, call=0, rs=None):
     gm, gt = ar.out(R * D, dtype), ar.out(R * D * D, dtype)
-    rc = lib.raw("zs_mvn_sample_logprob_bwd" + sfx(dtype), _ptr(tril), _ptr(eps), _ptr(gz), _ptr(glp), reparam, _ptr(gm), _ptr(gt),
-                 K, R, D, seed, call, _ptr(rs), _stream())
+    rc = lib.raw("zs_mvn_sample_logprob_bwd" + sfx(dtype), ptr(tril), ptr(eps), ptr(gz), ptr(glp), reparam, ptr(gm), ptr(gt),
+                 K, R, D, seed, call, ptr(rs), stream())
     return rc, gm, gt
 
 
 def v2(lib, dtype, ar, mean, tril, x, K, R, D):
     lp = ar.out(K * R, dtype)
-    rc = lib.raw("zs_mvn_logprob" + sfx(dtype), _ptr(mean), _ptr(tril), _ptr(x), x.numel(), _ptr(lp), K, R, D, _stream())
+    rc = lib.raw("zs_mvn_logprob" + sfx(dtype), ptr(mean), ptr(tril), ptr(x), x.numel(), ptr(lp), K, R, D, stream())
     return rc, lp
 
 
 def v2b(lib, dtype, ar, mean, tril, x, glp, K, R, D):
     gx, gm, gt = ar.out(K * R * D, dtype), ar.out(R * D, dtype), ar.out(R * D * D, dtype)
-    rc = lib.raw("zs_mvn_logprob_bwd" + sfx(dtype), _ptr(mean), _ptr(tril), _ptr(x), x.numel(), _ptr(glp), _ptr(gx), _ptr(gm),
-                 _ptr(gt), K, R, D, _stream())
+    rc = lib.raw("zs_mvn_logprob_bwd" + sfx(dtype), ptr(mean), ptr(tril), ptr(x), x.numel(), ptr(glp), ptr(gx), ptr(gm),
+                 ptr(gt), K, R, D, stream())
     return rc, gx, gm, gt
 
 
@@ -249,7 +192,6 @@ def check_forward_and_backward(lib, D, R, K, dtypes=(F32, F64), shifts=(0, 1), d
                 o += list(v1b(lib, dtype, ar, dt, de, dgz, dg, 1, K, R, D))
                 o += list(v1b(lib, dtype, ar, dt, de, None, dg, 0, K, R, D))
                 (outs if rep == 0 else twice).extend(o)
-            torch.cuda.synchronize()
             ar.check_guards()
             for a, b in zip(outs, twice):
                 if isinstance(a, int):
@@ -316,7 +258,6 @@ def test_value_without_the_particle_axis_is_shared(lib):
             one, full = ar.put(x1, dtype), ar.put(x1[None].expand(K, R, D).contiguous(), dtype)
             pairs = [(v2(lib, dtype, ar, dm, dt, one, K, R, D), v2(lib, dtype, ar, dm, dt, full, K, R, D)),
                      (v2b(lib, dtype, ar, dm, dt, one, dg, K, R, D), v2b(lib, dtype, ar, dm, dt, full, dg, K, R, D))]
-            torch.cuda.synchronize()
             ar.check_guards()
             for got, want in pairs:
                 assert got[0] == 0 and want[0] == 0
@@ -332,17 +273,16 @@ def test_drawn_noise_is_the_main_librarys_normal_stream(lib, main_lib, D):
     for dtype in (F32, F64):
         for seed, call, state in ((11, 3, None), (0, 2, (77, 1 << 33))):
             rs = None if state is None else torch.tensor(state, dtype=I64, device=DEV)
-            stream = torch.empty(n, dtype=F32, device=DEV)
-            main_lib.call("zs_philox_normal_f32", stream.data_ptr(), n, seed, call, _ptr(rs), _stream())
+            noise = torch.empty(n, dtype=F32, device=DEV)
+            main_lib.call("zs_philox_normal_f32", noise.data_ptr(), n, seed, call, ptr(rs), stream())
             for shift in (0, 1):
                 ar = Arena(shift)
-                dm, dt, de = ar.put(d["mean"], dtype), ar.put(d["tril"], dtype), ar.put(stream.cpu(), dtype)
+                dm, dt, de = ar.put(d["mean"], dtype), ar.put(d["tril"], dtype), ar.put(noise.cpu(), dtype)
                 dg, dgz = ar.put(d["g"], dtype), ar.put(d["gz"], dtype)
                 pairs = [(v1(lib, dtype, ar, dm, dt, None, K, R, D, seed=seed, call=call, rs=rs), v1(lib, dtype, ar, dm, dt, de, K, R, D))]
                 for reparam in (1, 0):
                     pairs.append((v1b(lib, dtype, ar, dt, None, dgz, dg, reparam, K, R, D, seed=seed, call=call, rs=rs),
                                   v1b(lib, dtype, ar, dt, de, dgz, dg, reparam, K, R, D)))
-                torch.cuda.synchronize()
                 ar.check_guards()
                 for drawn, given in pairs:
                     assert drawn[0] == 0 and given[0] == 0
@@ -359,7 +299,6 @@ def test_a_bad_diagonal_gives_inf_or_nan_without_a_trap(lib):
     for dtype in (F32, F64):
         ar = Arena(0)
         rc, z, lp = v1(lib, dtype, ar, ar.put(d["mean"], dtype), ar.put(tril, dtype), ar.put(d["eps"], dtype), K, R, D)
-        torch.cuda.synchronize()
         ar.check_guards()
         lp = lp.cpu().view(K, R)
         assert rc == 0 and bool((lp[:, 0] == math.inf).all()) and bool(torch.isnan(lp[:, 1]).all()) and bool(torch.isfinite(lp[:, 2]).all())
@@ -372,7 +311,7 @@ def test_rejected_arguments_write_nothing(lib):
         ar = Arena(0)
         dm, dt, de, dg = ar.put(d["mean"], dtype), ar.put(d["tril"], dtype), ar.put(d["eps"], dtype), ar.put(d["g"], dtype)
         oz, ol, om, ot = ar.out(K * R * D, dtype), ar.out(K * R, dtype), ar.out(R * D, dtype), ar.out(R * D * D, dtype)
-        s, st, p = sfx(dtype), _stream(), _ptr
+        s, st, p = sfx(dtype), stream(), ptr
 
         def every(mp, tp, k, r, n):
             return [lib.raw("zs_mvn_sample_logprob" + s, p(mp), p(tp), p(de), p(oz), p(ol), k, r, n, 0, 0, None, st),
@@ -397,7 +336,6 @@ def test_rejected_arguments_write_nothing(lib):
         assert lib.raw("zs_mvn_sample_logprob_bwd" + s, p(dt), p(de), None, None, 1, p(om), p(ot), K, R, D, 0, 0, None, st) == EINVAL
         assert lib.raw("zs_mvn_sample_logprob_bwd" + s, p(dt), p(de), p(de), None, 0, p(om), p(ot), K, R, D, 0, 0, None, st) == EINVAL
         torch.cuda.synchronize()
-        for buf, o, n in ar.outs:
-            assert bool((buf == SENTINEL).all()), "a rejected call wrote something"
+        assert ar.untouched(), "a rejected call wrote something"
     assert lib.raw("zs_mvn_max_dim") == 64
     assert [lib.raw("zs_mvn_group_lanes", n) for n in (0, 1, 2, 3, 5, 33, 64, 65)] == [0, 1, 2, 4, 8, 64, 64, 0]

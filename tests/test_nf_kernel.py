@@ -12,14 +12,10 @@ import pytest
 import torch
 
 import nf_host
+from kernel_abi import EINVAL, ENOTSUP, F32, F64, Arena, load, ptr, same_bits, sfx, stream
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-EINVAL, ENOTSUP = -1, -2
-GUARD = 4
-SENTINEL = 777.0
-F32, F64 = torch.float32, torch.float64
 LD = np.longdouble
 DS = [1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 31, 32, 33, 40, 63, 64]
 RS = [1, 3, 65]
@@ -228,59 +224,7 @@ def householder_truth(inp, dtype):
 # ------------------------------------------------------------------------------------------------ device plumbing
 @pytest.fixture(scope="module")
 def lib():
-    from zhusuan import _nf_hip
-    return _nf_hip.lib(_nf_hip.LIB_PATH)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    from zhusuan import _hip
-    return _hip.stream_for(torch.empty(0, device=DEV))
-
-
-def sfx(dtype):
-    return "_f32" if dtype == F32 else "_f64"
-
-
-class Arena(object):
-    """Device operands inside guarded buffers: GUARD sentinels on both sides, `shift` more elements in front."""
-
-    def __init__(self, shift=0):
-        self.shift = shift
-        self.outs = []
-
-    def _buf(self, n, dtype):
-        o = GUARD + self.shift
-        return torch.full((o + n + GUARD,), SENTINEL, dtype=dtype, device=DEV), o
-
-    def put(self, a, dtype):
-        if a is None:
-            return None
-        t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
-        buf, o = self._buf(t.numel(), dtype)
-        buf[o:o + t.numel()] = t.reshape(-1).to(dtype).to(DEV)
-        return buf[o:o + t.numel()]
-
-    def out(self, n, dtype):
-        buf, o = self._buf(n, dtype)
-        self.outs.append((buf, o, n))
-        return buf[o:o + n]
-
-    def check_guards(self):
-        for buf, o, n in self.outs:
-            assert bool((buf[:o] == SENTINEL).all()) and bool((buf[o + n:] == SENTINEL).all()), "write outside the tensor"
-
-    def untouched(self):
-        return all(bool((buf == SENTINEL).all()) for buf, _, _ in self.outs)
-
-
-def same_bits(a, b):
-    a, b = a.cpu(), b.cpu()
-    it = torch.int32 if a.dtype == F32 else torch.int64
-    return torch.equal(a.view(it), b.view(it))
+    return load("nf")
 
 
 def assert_close(name, got, truth, tol):
@@ -297,7 +241,7 @@ def assert_close(name, got, truth, tol):
 
 # ------------------------------------------------------------------------------------------------ raw calls
 def call(lib, name, dtype, *args):
-    return lib.raw(name + sfx(dtype), *args, _stream())
+    return lib.raw(name + sfx(dtype), *args, stream())
 
 
 def n_workgroups(lib, R, D):
@@ -318,16 +262,16 @@ def run_planar(lib, dtype, inp, shift=0, gy=True, gld=True, want_y=True, want_ld
             x = ar.put(inp["x"], dtype)
         gx = ar.out(R * D, dtype) if want_gx else None
         partials = ar.out(n_wg * L * (2 * D + 2), dtype) if want_partials else None
-        assert call(lib, "zs_nf_planar_bwd", dtype, _ptr(u), _ptr(w), _ptr(b), _ptr(x), _ptr(gyt), _ptr(gldt), _ptr(gx),
-                    _ptr(partials), R, D, L) == 0
+        assert call(lib, "zs_nf_planar_bwd", dtype, ptr(u), ptr(w), ptr(b), ptr(x), ptr(gyt), ptr(gldt), ptr(gx),
+                    ptr(partials), R, D, L) == 0
         gu = gw = gb = None
         if want_partials:
             gu, gw, gb = ar.out(L * D, dtype), ar.out(L * D, dtype), ar.out(L, dtype)
-            assert call(lib, "zs_nf_planar_finish", dtype, _ptr(u), _ptr(w), _ptr(partials), n_wg, _ptr(gu), _ptr(gw), _ptr(gb),
+            assert call(lib, "zs_nf_planar_finish", dtype, ptr(u), ptr(w), ptr(partials), n_wg, ptr(gu), ptr(gw), ptr(gb),
                         D, L) == 0
-        y = x if alias else (ar.out(R * D, dtype) if want_y else None)
+        y = x.view(-1) if alias else (ar.out(R * D, dtype) if want_y else None)
         ld = ar.out(R, dtype) if want_ld else None
-        assert call(lib, "zs_nf_planar_fwd", dtype, _ptr(u), _ptr(w), _ptr(b), _ptr(x), _ptr(y), _ptr(ld), R, D, L) == 0
+        assert call(lib, "zs_nf_planar_fwd", dtype, ptr(u), ptr(w), ptr(b), ptr(x), ptr(y), ptr(ld), R, D, L) == 0
         torch.cuda.synchronize()
         now = dict(y=y, logdet=ld, gx=gx, partials=partials, gu=gu, gw=gw, gb=gb)
         for k, t in now.items():
@@ -348,9 +292,9 @@ def run_householder(lib, dtype, inp, shift=0, want_gx=True, want_gv=True, alias=
             x = ar.put(inp["x"], dtype)
         gx = ar.out(R * D, dtype) if want_gx else None
         gv = ar.out(L * R * D, dtype) if want_gv else None
-        assert call(lib, "zs_nf_householder_bwd", dtype, _ptr(v), _ptr(x), _ptr(gy), _ptr(gx), _ptr(gv), R, D, L) == 0
-        y = x if alias else ar.out(R * D, dtype)
-        assert call(lib, "zs_nf_householder_fwd", dtype, _ptr(v), _ptr(x), _ptr(y), R, D, L) == 0
+        assert call(lib, "zs_nf_householder_bwd", dtype, ptr(v), ptr(x), ptr(gy), ptr(gx), ptr(gv), R, D, L) == 0
+        y = x.view(-1) if alias else ar.out(R * D, dtype)
+        assert call(lib, "zs_nf_householder_fwd", dtype, ptr(v), ptr(x), ptr(y), R, D, L) == 0
         torch.cuda.synchronize()
         now = dict(hy=y, hgx=gx, hgv=gv)
         for k, t in now.items():
@@ -471,7 +415,7 @@ def test_rejected_arguments_write_nothing_and_empty_shapes_launch_nothing(lib):
         ar = Arena()
         u, w, b, x, v, gy, gld = (ar.put(inp[k], dtype) for k in ("u", "w", "b", "x", "v", "gy", "gld"))
         y, ld, gx, part, gu, gw, gb, gv = (ar.out(n, dtype) for n in (9, 3, 9, 16, 6, 6, 2, 18))
-        p = _ptr
+        p = ptr
 
         def fwd(u=u, w=w, b=b, x=x, y=y, ld=ld, R=3, D=3, L=2):
             return call(lib, "zs_nf_planar_fwd", dtype, p(u), p(w), p(b), p(x), p(y), p(ld), R, D, L)

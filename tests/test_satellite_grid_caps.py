@@ -25,11 +25,10 @@ import test_flow_kernel as TF
 import test_hmc_kernel as TH
 import test_klpq_kernel as TQ
 import test_mvn_kernel as TM
+from kernel_abi import DEV, F32, F64, SENTINEL, Arena, covered, load, load_main, ptr, same_bits, sfx, stream
 from test_size_gated_variants import _stops_the_session_on_a_device_fault as stops_on_fault
 
 gpu = pytest.mark.gpu
-DEV = "cuda:0"
-F32, F64, I64 = torch.float32, torch.float64, torch.int64
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 _MEMO = {}          # results of ONE pair at a time: the sibling test of a pair reads what its two sides left
@@ -42,22 +41,6 @@ def memo(pair_key, side_key, build):
     if side_key not in _MEMO:
         _MEMO[side_key] = build()
     return _MEMO[side_key]
-
-
-def bits_equal(a, b):
-    a, b = a.cpu().contiguous(), b.cpu().contiguous()
-    if a.dtype == I64:
-        return torch.equal(a, b)
-    it = torch.int32 if a.dtype == F32 else torch.int64
-    return a.shape == b.shape and torch.equal(a.view(it), b.view(it))
-
-
-def covered(outs, fill=777.0):
-    """No element of an output keeps the fill its buffer was created with."""
-    for t in outs:
-        if t is None:
-            continue
-        assert not bool((t == fill).any()), "an output element was never written"
 
 
 # =====================================================================================================================
@@ -243,14 +226,12 @@ def test_case_table_against_the_gates():
 # =====================================================================================================================
 @pytest.fixture(scope="module")
 def cat_lib():
-    from zhusuan import _cat_hip
-    return _cat_hip.lib(_cat_hip.LIB_PATH)
+    return load("cat")
 
 
 @pytest.fixture(scope="module")
 def main_lib():
-    from zhusuan import _hip
-    return _hip.KernelLibrary(_hip.LIB_PATH)
+    return load_main()
 
 
 def cat_rows(d, R):
@@ -312,7 +293,7 @@ def test_cat_leading_rows_are_the_one_trip_launch(cat_lib, ci, which):
             a = a.view(K, R, -1)[:, :R - 1].reshape(-1)
         else:                                        # summed over the particles: per row
             a = a.view(R, -1)[:R - 1].reshape(-1)
-        assert bits_equal(a, b), "the rows of the first trip differ from the one-trip launch (%s, %s)" % (name, which)
+        assert same_bits(a, b), "the rows of the first trip differ from the one-trip launch (%s, %s)" % (name, which)
 
 
 @gpu
@@ -325,22 +306,21 @@ def test_cat_drawn_noise_beyond_the_grid_cap(cat_lib, main_lib, ci):
         lg = TC.case_inputs(N, r, K, 1.0)["logits"]
         n = K * r * N
         seed, call = 11, 3
-        stream = torch.empty(n, dtype=F32, device=DEV)
-        main_lib.call("zs_philox_uniform_f32", stream.data_ptr(), n, seed, call, None, TC._stream())
-        ar = TC.Arena(0)
-        dl, du = ar.put(lg, F32), ar.put(stream.cpu(), F32)
+        noise = torch.empty(n, dtype=F32, device=DEV)
+        main_lib.call("zs_philox_uniform_f32", noise.data_ptr(), n, seed, call, None, stream())
+        ar = Arena(0)
+        dl, du = ar.put(lg, F32), ar.put(noise.cpu(), F32)
         drawn = TC.c1(cat_lib, F32, ar, dl, None, K, r, N, seed=seed, call=call)
         given = TC.c1(cat_lib, F32, ar, dl, du, K, r, N)
         rdrawn = TC.c3(cat_lib, F32, ar, dl, None, 0.5, 1, K, r, N, seed=seed, call=call)
         rgiven = TC.c3(cat_lib, F32, ar, dl, du, 0.5, 1, K, r, N)
-        torch.cuda.synchronize()
         ar.check_guards()
         for a, b in list(zip(drawn, given)) + list(zip(rdrawn, rgiven)):
             if isinstance(a, int):
                 assert a == 0 and b == 0
             else:
                 covered([a.cpu()])
-                assert bits_equal(a, b), "the in-kernel draw is not the injected Philox stream (%s, R=%d)" % (name, r)
+                assert same_bits(a, b), "the in-kernel draw is not the injected Philox stream (%s, R=%d)" % (name, r)
 
 
 @gpu
@@ -352,16 +332,15 @@ def test_cat_exp_beyond_the_grid_cap(cat_lib, n):
     name, N, R, K, _ = CAT[4]
     scale = 1.0
     d = TC.case_inputs(N, R, K, scale)
-    ar = TC.Arena(0)
+    ar = Arena(0)
     dl, du = ar.put(d["logits"], F32), ar.put(d["u"], F32)
     rc, y, ey, lp = TC.c3(cat_lib, F32, ar, dl, du, 0.5, 1, K, R, N)
     outs = [ar.out(n, F32) for _ in range(2)]
     for o in outs:
-        assert cat_lib.raw("zs_cat_exp_f32", TC._ptr(y), TC._ptr(o), n, TC._stream()) == 0
-    torch.cuda.synchronize()
+        assert cat_lib.raw("zs_cat_exp_f32", ptr(y), ptr(o), n, stream()) == 0
     ar.check_guards()
     covered([outs[0].cpu()])
-    assert rc == 0 and bits_equal(outs[0], outs[1]) and bits_equal(outs[0], ey[:n])
+    assert rc == 0 and same_bits(outs[0], outs[1]) and same_bits(outs[0], ey[:n])
 
 
 # =====================================================================================================================
@@ -369,8 +348,7 @@ def test_cat_exp_beyond_the_grid_cap(cat_lib, n):
 # =====================================================================================================================
 @pytest.fixture(scope="module")
 def mvn_lib():
-    from zhusuan import _mvn_hip
-    return _mvn_hip.lib(_mvn_hip.LIB_PATH)
+    return load("mvn")
 
 
 def mvn_rows(d, R):
@@ -409,30 +387,29 @@ def test_mvn_leading_rows_are_the_one_trip_launch(mvn_lib, pi):
     over, under = mvn_side(mvn_lib, pi, "over"), mvn_side(mvn_lib, pi, "under")
     for a, b in zip(over, under):
         a = a.view(K, R, -1)[:, :R - 1] if a.numel() in (K * R, K * R * D) else a.view(R, -1)[:R - 1]
-        assert bits_equal(a.reshape(-1), b), "the rows of the first trip differ from the one-trip launch (%s)" % name
+        assert same_bits(a.reshape(-1), b), "the rows of the first trip differ from the one-trip launch (%s)" % name
 
 
 def mvn_forward(lib, main_lib, d, D, R, K, drawn):
     """V1 (noise given, or drawn and compared with the launch that is given the main library's stream) and V2 on the leading K
     particles of `d`; returns (z, lp of V1, lp of V2) on the CPU."""
-    ar = TM.Arena(0)
+    ar = Arena(0)
     dm, dt, dx = ar.put(d["mean"], F32), ar.put(d["tril"], F32), ar.put(d["x"][:K], F32)
     seed, call = 11, 3
     if drawn:
         n = K * R * D
-        stream = torch.empty(n, dtype=F32, device=DEV)
-        main_lib.call("zs_philox_normal_f32", stream.data_ptr(), n, seed, call, None, TM._stream())
-        de = ar.put(stream.cpu(), F32)
+        noise = torch.empty(n, dtype=F32, device=DEV)
+        main_lib.call("zs_philox_normal_f32", noise.data_ptr(), n, seed, call, None, stream())
+        de = ar.put(noise.cpu(), F32)
         rc0, z0, lp0 = TM.v1(lib, F32, ar, dm, dt, None, K, R, D, seed=seed, call=call)
     else:
         de = ar.put(d["eps"][:K], F32)
     rc, z, lp = TM.v1(lib, F32, ar, dm, dt, de, K, R, D)
     rc2, lp2 = TM.v2(lib, F32, ar, dm, dt, dx, K, R, D)
-    torch.cuda.synchronize()
     ar.check_guards()
     assert rc == 0 and rc2 == 0
     if drawn:
-        assert rc0 == 0 and bits_equal(z0, z) and bits_equal(lp0, lp), "the in-kernel draw is not the injected Philox stream"
+        assert rc0 == 0 and same_bits(z0, z) and same_bits(lp0, lp), "the in-kernel draw is not the injected Philox stream"
     outs = [z.cpu().view(K, R, D), lp.cpu().view(K, R), lp2.cpu().view(K, R)]
     covered(outs)
     return outs
@@ -452,11 +429,11 @@ def test_mvn_particle_shares(mvn_lib, main_lib, si):
     for drawn in (False, True):
         full = mvn_forward(mvn_lib, main_lib, d, D, R, K, drawn)
         if not drawn:
-            assert bits_equal(full[0].reshape(-1), found[F32][0]) and bits_equal(full[1].reshape(-1), found[F32][1])
+            assert same_bits(full[0].reshape(-1), found[F32][0]) and same_bits(full[1].reshape(-1), found[F32][1])
         for k in smaller:
             part = mvn_forward(mvn_lib, main_lib, d, D, R, k, drawn)
             for a, b in zip(full, part):
-                assert bits_equal(a[:k], b), "the cut of the particles into shares changed a bit (%s, K' = %d)" % (name, k)
+                assert same_bits(a[:k], b), "the cut of the particles into shares changed a bit (%s, K' = %d)" % (name, k)
 
 
 @gpu
@@ -469,7 +446,7 @@ def test_mvn_leading_particles_beyond_the_grid_cap(mvn_lib, main_lib, pi):
     for drawn in (False, True):
         full, part = mvn_forward(mvn_lib, main_lib, d, D, R, K, drawn), mvn_forward(mvn_lib, main_lib, d, D, R, 1, drawn)
         for a, b in zip(full, part):
-            assert bits_equal(a[:1], b), "the leading particle differs from the launch with one particle (%s)" % name
+            assert same_bits(a[:1], b), "the leading particle differs from the launch with one particle (%s)" % name
 
 
 # =====================================================================================================================
@@ -477,8 +454,7 @@ def test_mvn_leading_particles_beyond_the_grid_cap(mvn_lib, main_lib, pi):
 # =====================================================================================================================
 @pytest.fixture(scope="module")
 def klpq_lib():
-    from zhusuan import _klpq_hip
-    return _klpq_hip.lib(_klpq_hip.LIB_PATH)
+    return load("klpq")
 
 
 def klpq_check(lib, K, B, Tp, Tq, layout, scale, dtypes):
@@ -488,9 +464,9 @@ def klpq_check(lib, K, B, Tp, Tq, layout, scale, dtypes):
         ref = runs[0]
         for name in ref:
             if tuple(runs[1][name].shape) == tuple(ref[name].shape):
-                assert TQ.same_bits(ref[name], runs[1][name]), "%s differs between layouts / alignments (K=%d B=%d %s)" % (name, K, B, layout)
+                assert same_bits(ref[name], runs[1][name]), "%s differs between layouts / alignments (K=%d B=%d %s)" % (name, K, B, layout)
         covered(ref.values())
-        tag = " [K=%d B=%d Tp=%d Tq=%d %s scale %g %s]" % (K, B, Tp, Tq, layout, scale, TQ.sfx(dtype))
+        tag = " [K=%d B=%d Tp=%d Tq=%d %s scale %g %s]" % (K, B, Tp, Tq, layout, scale, sfx(dtype))
         TQ.check_case(tag, dtype, d, K, B, ref, B <= TQ.MEAN_MAX_B)
     return d
 
@@ -524,7 +500,7 @@ def test_klpq_leading_datapoints_are_the_one_trip_launch(klpq_lib, pi, ci):
     name, K, B, combos = KLPQ_PAIRS[pi]
     Tp, Tq, layout, scale = combos[ci]
     d = TQ.case_inputs(K, B, Tp, Tq, layout, scale)
-    ar = TQ.Arena(0)
+    ar = Arena(0)
     tabs, keep = {}, []
     for side in ("p", "q"):
         tab = (KlpqTerm * len(d[side]))()
@@ -537,14 +513,13 @@ def test_klpq_leading_datapoints_are_the_one_trip_launch(klpq_lib, pi, ci):
     got = []
     for b in (B, B - 1, B):
         o = [ar.out(b * K, F32), ar.out(b, F32), ar.out(b, F32), ar.out(b, F32)]
-        assert klpq_lib.raw("zs_klpq_forward_f32", tabs["p"], Tp, tabs["q"], Tq, K, b, 0, *([TQ._ptr(t) for t in o] + [None, TQ._stream()])) == 0
+        assert klpq_lib.raw("zs_klpq_forward_f32", tabs["p"], Tp, tabs["q"], Tq, K, b, 0, *([ptr(t) for t in o] + [None, stream()])) == 0
         got.append(o)
-    torch.cuda.synchronize()
     ar.check_guards()
     for full, part, again in zip(*got):
         covered([full.cpu(), part.cpu()])
-        assert bits_equal(full, again), "two identical launches differ"
-        assert bits_equal(full[:part.numel()], part), "the datapoints of the first trip differ from the one-trip launch (%s)" % name
+        assert same_bits(full, again), "two identical launches differ"
+        assert same_bits(full[:part.numel()], part), "the datapoints of the first trip differ from the one-trip launch (%s)" % name
 
 
 KLPQ_MEAN_COMBOS = [(Tp, Tq, layout) for Tp, Tq in ((1, 1), (3, 2)) for layout in TQ.LAYOUTS]
@@ -565,8 +540,7 @@ def test_klpq_batch_mean_at_its_limit(klpq_lib, K, B):
 # =====================================================================================================================
 @pytest.fixture(scope="module")
 def hmc_lib():
-    from zhusuan import _hmc_hip
-    return _hmc_hip.lib(_hmc_hip.LIB_PATH)
+    return load("hmc")
 
 
 @gpu
@@ -576,7 +550,7 @@ def hmc_lib():
 def test_hmc_decide_beyond_one_pass(hmc_lib, C, dtype):
     """More chains than k_hmc_decide has threads: a thread accumulates the acceptance of two or three chains before the tree."""
     k, l0, l1, u, t, out, acc, st = TH.check_decide(hmc_lib, dtype, C, 1)
-    covered([out, st], fill=TH.SENTINEL)
+    covered([out, st], fill=SENTINEL)
     assert bool(((acc == 0) | (acc == 1)).all())
     out2, acc2, st2 = TH.run_decide(hmc_lib, dtype, C, k, l0, l1, u, TH.state_block(), adapting=1)
     assert torch.equal(out, out2) and torch.equal(acc, acc2) and torch.equal(st, st2), "two identical calls differ"
@@ -609,16 +583,13 @@ def test_hmc_select_beyond_the_grid_cap(hmc_lib, name, n, shift, dtype):
         want = q if accept else q0
         res = []
         for rep in range(2):
-            v0, b0 = TH.place(q0, [n], shift)
-            v1, b1 = TH.place(q, [n], shift)
-            vo, bo = TH.place(torch.full_like(q, float("nan")), [n], shift)
-            table = [dict(q0=v0[0], q=v1[0], q_out=vo[0], start=0, row=n)]
+            ar = Arena(shift)
+            v0, v1, vo = ar.put(q0), ar.put(q), ar.put(torch.full_like(q, float("nan")))
+            table = [dict(q0=v0, q=v1, q_out=vo, start=0, row=n)]
             assert TH.raw_select(hmc_lib, dtype, table, n, 1, acc) == 0
-            torch.cuda.synchronize()
-            for b in (b0, b1, bo):
-                TH.guards_intact(b)
-            res.append(vo[0].cpu())
-            assert torch.equal(v0[0].cpu(), q0) and torch.equal(v1[0].cpu(), q), "an input was modified"
+            ar.check_guards()
+            res.append(vo.cpu())
+            assert torch.equal(v0.cpu(), q0) and torch.equal(v1.cpu(), q), "an input was modified"
         assert torch.equal(res[0], want) and torch.equal(res[1], want)
 
 
@@ -673,8 +644,7 @@ def test_hmc_drawn_momentum_beyond_the_grid_cap(hmc_lib, side, n):
 # =====================================================================================================================
 @pytest.fixture(scope="module")
 def flow_lib():
-    from zhusuan import _flow_hip
-    return _flow_hip.lib(_flow_hip.LIB_PATH)
+    return load("flow")
 
 
 def flow_shapes(case, twin=False):
