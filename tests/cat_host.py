@@ -5,7 +5,7 @@ draw order, call ids, launch budget) runs on a GPU-less machine.  The package it
 
 The restatements evaluate the header's formulas in float64 and round the results to the tensors' dtype.  Where no noise is
 injected, the uniforms are flat elements of the C oracle's ``zs_philox_uniform_f32`` stream for the launch's (seed, call): the
-kernels' noise contract.  ``calls`` records every launch.
+kernels' noise contract.  ``recording()`` lists every launch (tests/host_routing.py).
 
 ``reference_*`` are the same formulas in pure float64 on float64 inputs, written with torch's own ``logsumexp`` / autograd: the
 truth of the kernel and distribution tests."""
@@ -15,18 +15,11 @@ import torch
 
 import host_routing
 
-calls = []
 F64 = torch.float64
 
 
 def philox_uniform(n, seed, call, rng_state=None):
     return host_routing.philox("zs_philox_uniform_f32", n, seed, call, rng_state)
-
-
-def _host_only(tensors):
-    for t in tensors:
-        if t is not None and t.device.type != "cpu":
-            raise RuntimeError("tests/cat_host: host restatement installed but tensor is on %s" % t.device)
 
 
 # ------------------------------------------------------------------------------------------------ the float64 truth
@@ -97,8 +90,7 @@ def _uniforms(logits, K, u, seed, call, rng_state):
 
 
 def sample_logprob(logits, K, u=None, seed=0, call=0, rng_state=None, want_index=True, want_onehot=False):
-    calls.append(("sample_logprob", K, tuple(logits.shape), call))
-    _host_only([logits, u, rng_state])
+    host_routing.host_only("cat_host", [logits, u, rng_state])
     R, N = logits.shape
     with torch.no_grad():
         idx, lp, _ = reference_sample(logits, _uniforms(logits, K, u, seed, call, rng_state))
@@ -111,8 +103,7 @@ def _rows(v, K, R, event):
 
 
 def logprob(logits, K, idx=None, x=None):
-    calls.append(("logprob", K, tuple(logits.shape)))
-    _host_only([logits, idx, x])
+    host_routing.host_only("cat_host", [logits, idx, x])
     R, N = logits.shape
     with torch.no_grad():
         if x is None:
@@ -121,8 +112,7 @@ def logprob(logits, K, idx=None, x=None):
 
 
 def logprob_bwd(logits, K, glp, idx=None, x=None, want_gx=False):
-    calls.append(("logprob_bwd", K, tuple(logits.shape)))
-    _host_only([logits, idx, x, glp])
+    host_routing.host_only("cat_host", [logits, idx, x, glp])
     R, N = logits.shape
     with torch.no_grad():
         lg, g = logits.to(F64), glp.to(F64).reshape(K, R)
@@ -141,8 +131,7 @@ def logprob_bwd(logits, K, glp, idx=None, x=None, want_gx=False):
 
 
 def relaxed_sample_logprob(logits, K, tau, exp_space, u=None, seed=0, call=0, rng_state=None):
-    calls.append(("relaxed_sample_logprob", K, tuple(logits.shape), call))
-    _host_only([logits, u, rng_state])
+    host_routing.host_only("cat_host", [logits, u, rng_state])
     with torch.no_grad():
         y, lp = reference_relaxed(logits, _uniforms(logits, K, u, seed, call, rng_state), tau, exp_space)
     return y.to(logits.dtype), (torch.exp(y).to(logits.dtype) if exp_space else None), lp.to(logits.dtype)
@@ -154,8 +143,7 @@ def _q(logits, y, tau):
 
 
 def relaxed_sample_logprob_bwd(logits, K, tau, exp_space, y, gy=None, gey=None, glp=None):
-    calls.append(("relaxed_sample_logprob_bwd", K, tuple(logits.shape)))
-    _host_only([logits, y, gy, gey, glp])
+    host_routing.host_only("cat_host", [logits, y, gy, gey, glp])
     R, N = logits.shape
     e = 1.0 if exp_space else 0.0
     with torch.no_grad():
@@ -172,16 +160,14 @@ def relaxed_sample_logprob_bwd(logits, K, tau, exp_space, y, gy=None, gey=None, 
 
 
 def relaxed_logprob(logits, K, tau, exp_space, y):
-    calls.append(("relaxed_logprob", K, tuple(logits.shape)))
-    _host_only([logits, y])
+    host_routing.host_only("cat_host", [logits, y])
     R, N = logits.shape
     with torch.no_grad():
         return reference_relaxed_logprob(logits, _rows(y, K, R, (N,)), tau, exp_space).to(logits.dtype)
 
 
 def relaxed_logprob_bwd(logits, K, tau, exp_space, y, glp, want_gy=True, want_glogits=True):
-    calls.append(("relaxed_logprob_bwd", K, tuple(logits.shape)))
-    _host_only([logits, y, glp])
+    host_routing.host_only("cat_host", [logits, y, glp])
     R, N = logits.shape
     e = 1.0 if exp_space else 0.0
     with torch.no_grad():
@@ -192,17 +178,10 @@ def relaxed_logprob_bwd(logits, K, tau, exp_space, y, glp, want_gy=True, want_gl
     return gy, glogits
 
 
-_router = host_routing.Router("zhusuan._cat_hip", {
+router = host_routing.Router("zhusuan._cat_hip", {
     "sample_logprob": sample_logprob, "logprob": logprob, "logprob_bwd": logprob_bwd,
     "relaxed_sample_logprob": relaxed_sample_logprob, "relaxed_sample_logprob_bwd": relaxed_sample_logprob_bwd,
     "relaxed_logprob": relaxed_logprob, "relaxed_logprob_bwd": relaxed_logprob_bwd})
-install, uninstall = _router.install, _router.uninstall
-
-
-import pytest  # noqa: E402
-
-
-@pytest.fixture
-def cdev(dev):
-    """The suite's ``dev`` fixture (host and hip) with the categorical binding routed accordingly."""
-    yield from host_routing.routed(_router, dev)
+install, uninstall, recording = router.install, router.uninstall, router.recording
+# the suite's ``dev`` fixture (host and hip) with the categorical binding routed accordingly: imported by the tests
+cdev = host_routing.dev_fixture("cdev", router)

@@ -4,9 +4,8 @@ restatement of the contract of include/zs_flow.h on CPU tensors, so that the lay
 semantics, launch counts, shapes) runs on a GPU-less machine.  The package itself contains no such routing.
 
 The restatement is written in the tensors' own dtype, one torch op per operation of the header, in the header's order (no
-fused multiply-add).  ``count_launches()`` wraps whatever functions are currently installed -- the real ones on the hip
-back-end -- and counts their calls by name."""
-import contextlib
+fused multiply-add).  ``count_launches()`` (``Router.count`` of tests/host_routing.py) wraps whatever functions are
+currently installed -- the real ones on the hip back-end -- and counts their calls by name."""
 import math
 
 import torch
@@ -21,11 +20,10 @@ LOGDET_NONE, LOGDET_SCALAR, LOGDET_ROWS = 0, 1, 2
 
 
 def _host(*tensors):
+    host_routing.host_only("flow_host", tensors)
     for t in tensors:
         if t is None:
             continue
-        if t.device.type != "cpu":
-            raise RuntimeError("tests/flow_host: host restatement installed but tensor is on %s" % t.device)
         if t.dtype not in (torch.float32, torch.float64):
             raise RuntimeError("zhusuan.invertible: tensors must be float32 or float64, got %s" % t.dtype)
         if not t.is_contiguous():
@@ -166,36 +164,7 @@ def tail_bwd(base, g, z, loc, scale, param_rows, gz, g_logdet):
             g_logdet.copy_(g)
 
 
-_router = host_routing.Router("zhusuan._flow_hip", {n: globals()[n] for n in NAMES})
-install, uninstall = _router.install, _router.uninstall
-
-
-@contextlib.contextmanager
-def count_launches():
-    """``with count_launches() as c:`` -- c[name] counts the calls of every ``_flow_hip`` kernel function made inside."""
-    from zhusuan import _flow_hip
-    counts = {n: 0 for n in NAMES}
-    before = {n: getattr(_flow_hip, n) for n in NAMES}
-
-    def wrap(n, f):
-        def g(*a, **k):
-            counts[n] += 1
-            return f(*a, **k)
-        return g
-
-    for n, f in before.items():
-        setattr(_flow_hip, n, wrap(n, f))
-    try:
-        yield counts
-    finally:
-        for n, f in before.items():
-            setattr(_flow_hip, n, f)
-
-
-import pytest  # noqa: E402
-
-
-@pytest.fixture
-def fdev(dev):
-    """The suite's ``dev`` fixture (host and hip) with the flow kernels routed accordingly: imported by the flow tests."""
-    yield from host_routing.routed(_router, dev)
+router = host_routing.Router("zhusuan._flow_hip", {n: globals()[n] for n in NAMES})
+install, uninstall, count_launches = router.install, router.uninstall, router.count
+# the suite's ``dev`` fixture (host and hip) with the flow kernels routed accordingly: imported by the tests
+fdev = host_routing.dev_fixture("fdev", router)

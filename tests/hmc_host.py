@@ -7,7 +7,7 @@ The restatement is written in the tensors' own dtype in the operation order of t
 the leapfrog's a + b * c rounds twice where the kernel rounds once); the kinetic sum of a (tensor, chain) goes, in that dtype,
 into the first of the tensor's slots of the workspace and zeros into the others; ``decide`` is in float64.  Where a tensor
 brings no injected noise its momenta are flat elements of the C oracle's ``zs_philox_normal_f32`` stream for the launch's
-(seed, call), and ``u`` those of ``zs_philox_uniform_f32``: the kernels' noise contract.  ``calls`` records every launch.
+(seed, call), and ``u`` those of ``zs_philox_uniform_f32``: the kernels' noise contract.
 
 ``reference_iteration`` is a pure float64 HMC iteration (no workspace, no state block): the truth of the sampler tests."""
 import math
@@ -16,7 +16,6 @@ import torch
 
 import host_routing
 
-calls = []
 
 BEGIN, STEP, END = 0, 1, 2
 MAX_TENSORS, MAX_CHUNKS, TILE = 32, 16, 1024
@@ -36,21 +35,14 @@ def pieces(row):
     return (int(row) + TILE - 2) // TILE + 1
 
 
-def _host_only(tensors):
-    for t in tensors:
-        if t is not None and t.device.type != "cpu":
-            raise RuntimeError("tests/hmc_host: host restatement installed but tensor is on %s" % t.device)
-
-
 def move(kind, n_chains, state, q, p, grad, q0=None, z=None, p0=None, ksum=None, seed=0, call=0, rng_state=None, library=None):
-    calls.append(("move", kind, len(q), call))
     if len(q) > MAX_TENSORS:
         raise RuntimeError("zs_hmc_move failed with code -2: not supported (ZS_ENOTSUP)")
     if not q:
         return
     if kind not in (BEGIN, STEP, END):
         raise RuntimeError("zs_hmc_move failed with code -1: invalid argument (ZS_EINVAL)")
-    _host_only(list(q) + list(p) + list(grad) + list(q0 or []) + list(z or []) + list(p0 or []) + [state, ksum, rng_state])
+    host_routing.host_only("hmc_host", list(q) + list(p) + list(grad) + list(q0 or []) + list(z or []) + list(p0 or []) + [state, ksum, rng_state])
     C = int(n_chains)
     sizes = [t.numel() for t in q]
     rows = [k // C for k in sizes]
@@ -116,11 +108,10 @@ def decide_math(k0, k1, logp0, logp1, u, state, adapting, delta, gamma, t0, kapp
 
 def decide(chunks, n_chains, logp0, logp1, u, state, out, accept, adapting, delta, gamma, t0, kappa, seed=0, call=0,
            rng_state=None, library=None):
-    calls.append(("decide", len(chunks), call))
     if len(chunks) > MAX_CHUNKS:
         raise RuntimeError("zs_hmc_decide failed with code -2: not supported (ZS_ENOTSUP)")
     C = int(n_chains)
-    _host_only([logp0, logp1, u, state, out, accept, rng_state] + [t for c in chunks for t in c[:2]])
+    host_routing.host_only("hmc_host", [logp0, logp1, u, state, out, accept, rng_state] + [t for c in chunks for t in c[:2]])
     k0 = sum(c[0].view(C, c[2]).double().sum(dim=1) for c in chunks) * 0.5
     k1 = sum(c[1].view(C, c[2]).double().sum(dim=1) for c in chunks) * 0.5
     uu = u.double() if u is not None else philox_uniform(C, seed, call, rng_state).double()
@@ -133,10 +124,9 @@ def decide(chunks, n_chains, logp0, logp1, u, state, out, accept, adapting, delt
 
 
 def select(n_chains, q0, q, q_out, accept, library=None):
-    calls.append(("select", len(q)))
     if not q:
         return
-    _host_only(list(q0) + list(q) + list(q_out) + [accept])
+    host_routing.host_only("hmc_host", list(q0) + list(q) + list(q_out) + [accept])
     C = int(n_chains)
     with torch.no_grad():
         for a, b, o in zip(q0, q, q_out):
@@ -144,8 +134,8 @@ def select(n_chains, q0, q, q_out, accept, library=None):
             o.copy_(torch.where(m, b.reshape(C, -1), a.reshape(C, -1)).reshape(o.shape))
 
 
-_router = host_routing.Router("zhusuan._hmc_hip", {"move": move, "decide": decide, "select": select})
-install, uninstall = _router.install, _router.uninstall
+router = host_routing.Router("zhusuan._hmc_hip", {"move": move, "decide": decide, "select": select})
+install, uninstall = router.install, router.uninstall
 
 
 # ------------------------------------------------------------------------------------------------ the float64 truth
@@ -174,10 +164,5 @@ def reference_iteration(logp_and_grad, q0, z, u, eps, n_leapfrogs):
     return dict(q=sel, accept=acc, a=a, dh=dh, h0=k0 - l0, h1=k1 - l1, logp0=l0, logp1=l1)
 
 
-import pytest  # noqa: E402
-
-
-@pytest.fixture
-def hdev(dev):
-    """The suite's ``dev`` fixture (host and hip) with the HMC binding routed accordingly: imported by the sampler tests."""
-    yield from host_routing.routed(_router, dev)
+# the suite's ``dev`` fixture (host and hip) with the HMC binding routed accordingly: imported by the tests
+hdev = host_routing.dev_fixture("hdev", router)

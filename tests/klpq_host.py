@@ -3,22 +3,15 @@ the binding (``zhusuan._klpq_hip.forward`` / ``backward``) by torch restatements
 CPU tensors, so that the host logic of the objective (layouts, term tables, autograd wiring, launch budget) runs on a GPU-less
 machine.  The package itself contains no such routing.
 
-The restatements evaluate the header's formulas in float64 and round the results to the tensors' dtype.  ``calls`` records every
-launch.  ``reference_*`` are the same formulas in pure float64 on float64 inputs: the truth of the kernel and objective tests."""
+The restatements evaluate the header's formulas in float64 and round the results to the tensors' dtype.  ``recording()`` lists
+every launch (tests/host_routing.py).  ``reference_*`` are the same formulas in pure float64 on float64 inputs: the truth of the kernel and objective tests."""
 import math
 
 import torch
 
 import host_routing
 
-calls = []
 F64 = torch.float64
-
-
-def _host_only(tensors):
-    for t in tensors:
-        if t is not None and t.device.type != "cpu":
-            raise RuntimeError("tests/klpq_host: host restatement installed but tensor is on %s" % t.device)
 
 
 # ------------------------------------------------------------------------------------------------ the float64 truth
@@ -65,8 +58,7 @@ def reduce_to(g, shape):
 
 # ------------------------------------------------------------------------------------------------ the routed binding
 def forward(terms_p, terms_q, K, B, model_grad=False, bound_only=False, want_mean=False):
-    calls.append(("forward", K, B, len(terms_p), len(terms_q), dict(model_grad=model_grad, bound_only=bound_only, want_mean=want_mean)))
-    _host_only(list(terms_p) + list(terms_q))
+    host_routing.host_only("klpq_host", list(terms_p) + list(terms_q))
     dtype = terms_q[0].dtype
     with torch.no_grad():
         r = reference_forward(terms_p, terms_q, K, B, model_grad)
@@ -77,8 +69,7 @@ def forward(terms_p, terms_q, K, B, model_grad=False, bound_only=False, want_mea
 
 
 def backward(layouts_p, layouts_q, want_p, want_q, K, B, w, gcost, gbound=None, model_grad=False, gcost_is_mean=False):
-    calls.append(("backward", K, B, sum(map(bool, want_p)), sum(map(bool, want_q)), dict(model_grad=model_grad, gcost_is_mean=gcost_is_mean)))
-    _host_only([w, gcost, gbound])
+    host_routing.host_only("klpq_host", [w, gcost, gbound])
     with torch.no_grad():
         gq, gp = reference_backward(w, gcost, gbound, model_grad, B, gcost_is_mean)
 
@@ -92,14 +83,7 @@ def backward(layouts_p, layouts_q, want_p, want_q, K, B, w, gcost, gbound=None, 
         return ([give(lay, wnt, gp) for lay, wnt in zip(layouts_p, want_p)], [give(lay, wnt, gq) for lay, wnt in zip(layouts_q, want_q)])
 
 
-_router = host_routing.Router("zhusuan._klpq_hip", {"forward": forward, "backward": backward})
-install, uninstall = _router.install, _router.uninstall
-
-
-import pytest  # noqa: E402
-
-
-@pytest.fixture
-def kdev(dev):
-    """The suite's ``dev`` fixture (host and hip) with the inclusive-KL binding routed accordingly."""
-    yield from host_routing.routed(_router, dev)
+router = host_routing.Router("zhusuan._klpq_hip", {"forward": forward, "backward": backward})
+install, uninstall, recording = router.install, router.uninstall, router.recording
+# the suite's ``dev`` fixture (host and hip) with the inclusive-KL binding routed accordingly: imported by the tests
+kdev = host_routing.dev_fixture("kdev", router)

@@ -5,14 +5,12 @@ buffers, call ids) runs on a GPU-less machine.  The package itself contains no s
 
 The restatement is written in the tensors' own dtype in the operation order of the header.  Where a tensor brings no injected
 noise its standard normals are flat elements [start, start + numel) of the C oracle's ``zs_philox_normal_f32`` stream for the
-launch's (seed, call): the kernel's noise contract.  ``calls`` records (kind, number of tensors) of every launch."""
+launch's (seed, call): the kernel's noise contract."""
 import math
 
 import torch
 
 import host_routing
-
-calls = []
 
 SGLD, PSGLD, SGHMC_PRE, SGHMC_POST = 0, 1, 2, 3
 SECOND_ORDER, RESAMPLE_V = 1, 2
@@ -26,14 +24,11 @@ def philox_normal(n, seed, call, rng_state=None):
 
 def update(kind, q_in, q_out, grad=None, state=None, z=None, lr=0., decay=0., epsilon=0., alpha=0., beta=0., flags=0,
            seed=0, call=0, rng_state=None, library=None):
-    calls.append((kind, len(q_in)))
     if len(q_in) > MAX_TENSORS:
         raise RuntimeError("zs_mcmc_update failed with code -2: not supported (ZS_ENOTSUP)")
     if not q_in:
         return
-    for t in list(q_in) + list(q_out) + list(grad or []) + list(state or []) + [u for u in (z or []) if u is not None]:
-        if t.device.type != "cpu":
-            raise RuntimeError("tests/mcmc_host: host restatement installed but tensor is on %s" % t.device)
+    host_routing.host_only("mcmc_host", [q_in, q_out, grad or [], state or [], z or []])
     second, resample = bool(flags & SECOND_ORDER), bool(flags & RESAMPLE_V)
     draws = kind != SGHMC_PRE or resample
     sizes = [q.numel() for q in q_in]
@@ -78,14 +73,7 @@ def update(kind, q_in, q_out, grad=None, state=None, z=None, lr=0., decay=0., ep
             start += sizes[i]
 
 
-_router = host_routing.Router("zhusuan._mcmc_hip", {"update": update})
-install, uninstall = _router.install, _router.uninstall
-
-
-import pytest  # noqa: E402
-
-
-@pytest.fixture
-def mdev(dev):
-    """The suite's ``dev`` fixture (host and hip) with the samplers' update routed accordingly: imported by the sampler tests."""
-    yield from host_routing.routed(_router, dev)
+router = host_routing.Router("zhusuan._mcmc_hip", {"update": update})
+install, uninstall = router.install, router.uninstall
+# the suite's ``dev`` fixture (host and hip) with the samplers' update routed accordingly: imported by the tests
+mdev = host_routing.dev_fixture("mdev", router)

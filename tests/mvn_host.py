@@ -5,7 +5,7 @@ order, call ids, launch budget) runs on a GPU-less machine.  The package itself 
 
 The restatements evaluate the header's formulas in float64 and round the results to the tensors' dtype.  Where no noise is
 injected, the normals are flat elements of the C oracle's ``zs_philox_normal_f32`` stream for the launch's (seed, call): the
-kernels' noise contract.  ``calls`` records every launch.
+kernels' noise contract.  ``recording()`` lists every launch (tests/host_routing.py).
 
 ``reference_*`` are the same formulas in pure float64 on float64 inputs: the truth of the kernel and distribution tests.  They
 read the lower triangle only (``torch.tril``)."""
@@ -15,19 +15,12 @@ import torch
 
 import host_routing
 
-calls = []
 F64 = torch.float64
 LOG_2PI = math.log(2.0 * math.pi)
 
 
 def philox_normal(n, seed, call, rng_state=None):
     return host_routing.philox("zs_philox_normal_f32", n, seed, call, rng_state)
-
-
-def _host_only(tensors):
-    for t in tensors:
-        if t is not None and t.device.type != "cpu":
-            raise RuntimeError("tests/mvn_host: host restatement installed but tensor is on %s" % t.device)
 
 
 # ------------------------------------------------------------------------------------------------ the float64 truth
@@ -104,8 +97,7 @@ def _rows(x, K, R, D):
 
 
 def sample_logprob(mean, tril, K, eps=None, seed=0, call=0, rng_state=None):
-    calls.append(("sample_logprob", K, tuple(tril.shape), call))
-    _host_only([mean, tril, eps, rng_state])
+    host_routing.host_only("mvn_host", [mean, tril, eps, rng_state])
     with torch.no_grad():
         z, lp = reference_sample(mean, tril, _normals(tril, K, eps, seed, call, rng_state))
     return z.to(mean.dtype), lp.to(mean.dtype)
@@ -113,8 +105,7 @@ def sample_logprob(mean, tril, K, eps=None, seed=0, call=0, rng_state=None):
 
 def sample_logprob_bwd(tril, K, reparameterized, eps=None, seed=0, call=0, rng_state=None, gz=None, glp=None, want_gmean=True,
                        want_gtril=True):
-    calls.append(("sample_logprob_bwd", K, tuple(tril.shape), call))
-    _host_only([tril, eps, gz, glp, rng_state])
+    host_routing.host_only("mvn_host", [tril, eps, gz, glp, rng_state])
     R, D, _ = tril.shape
     with torch.no_grad():
         e = _normals(tril, K, eps, seed, call, rng_state)
@@ -128,16 +119,14 @@ def sample_logprob_bwd(tril, K, reparameterized, eps=None, seed=0, call=0, rng_s
 
 
 def logprob(mean, tril, K, x):
-    calls.append(("logprob", K, tuple(tril.shape)))
-    _host_only([mean, tril, x])
+    host_routing.host_only("mvn_host", [mean, tril, x])
     R, D, _ = tril.shape
     with torch.no_grad():
         return reference_logprob(mean, tril, _rows(x, K, R, D)).to(mean.dtype)
 
 
 def logprob_bwd(mean, tril, K, x, glp, want_gx=True, want_gmean=True, want_gtril=True):
-    calls.append(("logprob_bwd", K, tuple(tril.shape)))
-    _host_only([mean, tril, x, glp])
+    host_routing.host_only("mvn_host", [mean, tril, x, glp])
     R, D, _ = tril.shape
     with torch.no_grad():
         y = reference_whiten(mean, tril, _rows(x, K, R, D))
@@ -147,15 +136,8 @@ def logprob_bwd(mean, tril, K, x, glp, want_gx=True, want_gmean=True, want_gtril
     return gx, (gmean.to(mean.dtype) if want_gmean else None), (gtril.to(mean.dtype) if want_gtril else None)
 
 
-_router = host_routing.Router("zhusuan._mvn_hip", {
+router = host_routing.Router("zhusuan._mvn_hip", {
     "sample_logprob": sample_logprob, "sample_logprob_bwd": sample_logprob_bwd, "logprob": logprob, "logprob_bwd": logprob_bwd})
-install, uninstall = _router.install, _router.uninstall
-
-
-import pytest  # noqa: E402
-
-
-@pytest.fixture
-def vdev(dev):
-    """The suite's ``dev`` fixture (host and hip) with the multivariate-normal binding routed accordingly."""
-    yield from host_routing.routed(_router, dev)
+install, uninstall, recording = router.install, router.uninstall, router.recording
+# the suite's ``dev`` fixture (host and hip) with the multivariate-normal binding routed accordingly: imported by the tests
+vdev = host_routing.dev_fixture("vdev", router)

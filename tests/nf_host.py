@@ -4,27 +4,17 @@ on CPU tensors, so that the host logic of the modules (shapes, chunking, autogra
 GPU-less machine.  The package itself contains no such routing.
 
 The restatements evaluate the header's formulas in float64 and round the results to the tensors' dtype; the host ``planar_bwd``
-returns the row sums as the partials of ONE workgroup.  ``recording()`` wraps the five functions the binding holds at that
-moment -- the restatements on the host, the real ones on the GPU -- and lists every call as ``(name, args, kwargs)`` with each
-tensor replaced by its shape: the launch budget and the NULL operands of the modules read the same way on both.
+returns the row sums as the partials of ONE workgroup.  ``recording()`` (tests/host_routing.py) wraps the five functions the binding
+holds at that moment -- the restatements on the host, the real ones on the GPU -- and lists every call as ``(name, args, kwargs)``
+with each tensor replaced by its shape: the launch budget and the NULL operands of the modules read the same way on both.
 
 ``reference_*`` are the same formulas in pure float64 on float64 inputs: the truth of the kernel and module tests."""
-import contextlib
-import importlib
-
 import torch
 import torch.nn.functional as F
 
 import host_routing
 
-NAMES = ("planar_fwd", "planar_bwd", "planar_finish", "householder_fwd", "householder_bwd")
 F64 = torch.float64
-
-
-def _host_only(tensors):
-    for t in tensors:
-        if t is not None and t.device.type != "cpu":
-            raise RuntimeError("tests/nf_host: host restatement installed but tensor is on %s" % t.device)
 
 
 # ------------------------------------------------------------------------------------------------ the float64 truth
@@ -106,14 +96,14 @@ def reference_householder_bwd(v, x, gy):
 
 # ------------------------------------------------------------------------------------------------ the routed binding
 def planar_fwd(u, w, b, x, want_y=True, want_logdet=True):
-    _host_only([u, w, b, x])
+    host_routing.host_only("nf_host", [u, w, b, x])
     with torch.no_grad():
         y, ld = reference_planar_fwd(u, w, b, x)
     return (y.to(x.dtype) if want_y else None), (ld.to(x.dtype) if want_logdet else None)
 
 
 def planar_bwd(u, w, b, x, gy=None, gld=None, want_gx=True, want_partials=True):
-    _host_only([u, w, b, x, gy, gld])
+    host_routing.host_only("nf_host", [u, w, b, x, gy, gld])
     assert gy is not None or gld is not None and (want_gx or want_partials)
     with torch.no_grad():
         gx, Guh, Gw, Gb, Gc = reference_planar_bwd(u, w, b, x, gy, gld)
@@ -122,7 +112,7 @@ def planar_bwd(u, w, b, x, gy=None, gld=None, want_gx=True, want_partials=True):
 
 
 def planar_finish(u, w, partials, want_gu=True, want_gw=True, want_gb=True):
-    _host_only([u, w, partials])
+    host_routing.host_only("nf_host", [u, w, partials])
     D = u.shape[1]
     with torch.no_grad():
         P = partials.to(F64).sum(0)
@@ -131,51 +121,21 @@ def planar_finish(u, w, partials, want_gu=True, want_gw=True, want_gb=True):
 
 
 def householder_fwd(v, x):
-    _host_only([v, x])
+    host_routing.host_only("nf_host", [v, x])
     with torch.no_grad():
         return reference_householder_fwd(v, x).to(x.dtype)
 
 
 def householder_bwd(v, x, gy, want_gx=True, want_gv=True):
-    _host_only([v, x, gy])
+    host_routing.host_only("nf_host", [v, x, gy])
     with torch.no_grad():
         gx, gv = reference_householder_bwd(v, x, gy)
     return (gx.to(x.dtype) if want_gx else None), (gv.to(x.dtype) if want_gv else None)
 
 
-_router = host_routing.Router("zhusuan._nf_hip", {
+router = host_routing.Router("zhusuan._nf_hip", {
     "planar_fwd": planar_fwd, "planar_bwd": planar_bwd, "planar_finish": planar_finish, "householder_fwd": householder_fwd,
     "householder_bwd": householder_bwd})
-install, uninstall = _router.install, _router.uninstall
-
-
-@contextlib.contextmanager
-def recording():
-    """The list of calls ``(name, args, kwargs)`` made through the binding inside the block, tensors as their shapes."""
-    module = importlib.import_module("zhusuan._nf_hip")
-    calls, saved = [], {n: getattr(module, n) for n in NAMES}
-
-    def shape(a):
-        return tuple(a.shape) if isinstance(a, torch.Tensor) else a
-
-    def wrap(name, fn):
-        def recorded(*args, **kwargs):
-            calls.append((name, tuple(shape(a) for a in args), {k: shape(a) for k, a in kwargs.items()}))
-            return fn(*args, **kwargs)
-        return recorded
-    for n, fn in saved.items():
-        setattr(module, n, wrap(n, fn))
-    try:
-        yield calls
-    finally:
-        for n, fn in saved.items():
-            setattr(module, n, fn)
-
-
-import pytest  # noqa: E402
-
-
-@pytest.fixture
-def ndev(dev):
-    """The suite's ``dev`` fixture (host and hip) with the flow-stack binding routed accordingly."""
-    yield from host_routing.routed(_router, dev)
+install, uninstall, recording = router.install, router.uninstall, router.recording
+# the suite's ``dev`` fixture (host and hip) with the flow-stack binding routed accordingly: imported by the tests
+ndev = host_routing.dev_fixture("ndev", router)

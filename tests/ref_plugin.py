@@ -1,6 +1,7 @@
-"""pytest plugin used only by tests/test_reference_suite.py: makes `import zhusuan` resolve to THIS package
-and routes its kernel calls to the CPU oracle library, so the reference's own unittest files can run
-against it on a GPU-less machine."""
+"""pytest plugin used only by tests/reference_runs.py: makes `import zhusuan` resolve to THIS package and routes its kernel
+calls to the CPU oracle library, so the reference's own unittest files can run against it on a GPU-less machine.  ZS_REF_SUITE
+names the suite: "flow" adds the torch restatement of tests/flow_host.py and fixes the torch seed (ZS_FLOW_SUITE_SEED); "mcmc"
+adds that of tests/mcmc_host.py and fixes the torch seed and the host Philox seed (ZS_MCMC_SUITE_SEED)."""
 import os
 import sys
 
@@ -18,3 +19,12 @@ def pytest_configure(config):
     import conftest
     import host_backend
     host_backend.install(conftest.host_kernel_library())
+    suite = os.environ.get("ZS_REF_SUITE", "")
+    if suite:
+        import importlib
+        import torch
+        seed = int(os.environ.get("ZS_%s_SUITE_SEED" % suite.upper(), "0"))
+        torch.manual_seed(seed)
+        if suite == "mcmc":
+            host_backend.manual_seed(seed)
+        importlib.import_module(suite + "_host").install()

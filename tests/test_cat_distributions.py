@@ -18,6 +18,7 @@ from zhusuan.variational.importance_weighted_objective import ImportanceWeighted
 import cat_host
 import host_backend
 from cat_host import cdev  # noqa: F401
+from truth import gen, held_to_the_rule, seed_all
 
 F32, F64 = torch.float32, torch.float64
 FAMILIES = [Categorical, OnehotCategorical, ExpConcrete, Concrete]
@@ -29,18 +30,13 @@ def make(cls, logits, tau=0.7, **kw):
     return cls(logits, **kw)
 
 
-def seed_all(s):
-    torch.manual_seed(s)
-    host_backend.manual_seed(s)
-
-
 def rand_logits(shape, seed, dev, dtype=F32):
-    g = torch.Generator().manual_seed(seed)
+    g = gen(seed)
     return (1.5 * torch.randn(shape, generator=g, dtype=F64)).to(dtype).to(dev)
 
 
 def rand_u(shape, seed, dtype=F32):
-    g = torch.Generator().manual_seed(seed)
+    g = gen(seed)
     return ((torch.randint(0, 1 << 23, shape, generator=g).double() + 0.5) * 2.0 ** -23).to(dtype)
 
 
@@ -172,26 +168,26 @@ def test_few_rows_and_many_observations_go_to_the_kernels_as_rows(cdev, cls):
     row in turn, so the batch is presented as 40 rows of one particle; value and gradient are those of torch.distributions."""
     N, B, tau = 6, 40, 0.7
     lg = rand_logits((N,), 120, "cpu")
-    g = torch.randn(B, generator=torch.Generator().manual_seed(121))
+    g = torch.randn(B, generator=gen(121))
     if cls is Categorical:
-        v = torch.randint(0, N, (B,), generator=torch.Generator().manual_seed(122))
+        v = torch.randint(0, N, (B,), generator=gen(122))
     elif cls is OnehotCategorical:
-        v = torch.nn.functional.one_hot(torch.randint(0, N, (B,), generator=torch.Generator().manual_seed(122)), N).float()
+        v = torch.nn.functional.one_hot(torch.randint(0, N, (B,), generator=gen(122)), N).float()
     else:
-        v = torch.log_softmax(torch.randn(B, N, generator=torch.Generator().manual_seed(122)), -1)
+        v = torch.log_softmax(torch.randn(B, N, generator=gen(122)), -1)
         v = v if cls is ExpConcrete else torch.exp(v)
     l64 = lg.double().requires_grad_(True)
     want = torch_log_prob(cls, l64, v.double() if v.is_floating_point() else v, tau)
     gwant, = torch.autograd.grad(want, [l64], g.double())
-    del cat_host.calls[:]
     l0 = lg.to(cdev).requires_grad_(True)
-    lp = make(cls, l0, tau=tau).log_prob(v.to(cdev))
-    got, = torch.autograd.grad(lp, [l0], g.to(cdev))
+    with cat_host.recording() as calls:
+        lp = make(cls, l0, tau=tau).log_prob(v.to(cdev))
+        got, = torch.autograd.grad(lp, [l0], g.to(cdev))
     assert tuple(lp.shape) == (B,)
     assert float((lp.detach().cpu().double() - want.detach()).abs().max()) < 2e-5
     assert float((got.cpu().double() - gwant).abs().max()) < 2e-5 * (1 + float(gwant.abs().max()))
-    if cdev.type == "cpu":
-        assert [(c[0], c[1], c[2]) for c in cat_host.calls] == [(n, 1, (B, N)) for n in (cat_host.calls[0][0], cat_host.calls[1][0])]
+    # (name, K, the logits' shape) of a forward and a backward launch
+    assert [(c.name, c.args[1], c.args[0]) for c in calls] == [(n, 1, (B, N)) for n in (calls[0].name, calls[1].name)]
     # a handful of particles over many rows stays [K, R]
     from zhusuan.distributions.categorical import fold_particles
     assert fold_particles(40, 1, 6) and not fold_particles(5, 1, 6) and not fold_particles(50, 5120, 10) and not fold_particles(50, 256, 1000)
@@ -228,9 +224,9 @@ def test_log_prob_against_torch_distributions(cdev, cls, N):
     B, K, tau = 6, 4, 0.7
     lg = rand_logits((B, N), 10 + N, "cpu")
     if cls is Categorical:
-        v = torch.randint(0, N, (K, B), generator=torch.Generator().manual_seed(N))
+        v = torch.randint(0, N, (K, B), generator=gen(N))
     elif cls is OnehotCategorical:
-        v = torch.nn.functional.one_hot(torch.randint(0, N, (K, B), generator=torch.Generator().manual_seed(N)), N).float()
+        v = torch.nn.functional.one_hot(torch.randint(0, N, (K, B), generator=gen(N)), N).float()
     else:
         y = cat_host.reference_relaxed_y(lg, rand_u((K, B, N), 20 + N), tau).float()
         v = y if cls is ExpConcrete else torch.exp(y)
@@ -257,16 +253,16 @@ def test_gradients_against_float64_autograd(cdev, cls):
     B, K, N, tau = 5, 3, 7, 0.6
     lg = rand_logits((B, N), 31, "cpu")
     u = rand_u((K, B, N), 32)
-    g = torch.randn(K, B, generator=torch.Generator().manual_seed(33))
+    g = torch.randn(K, B, generator=gen(33))
     if cls is Categorical:
-        v = torch.randint(0, N, (K, B), generator=torch.Generator().manual_seed(34))
+        v = torch.randint(0, N, (K, B), generator=gen(34))
     elif cls is OnehotCategorical:
-        v = torch.rand(K, B, N, generator=torch.Generator().manual_seed(34))
+        v = torch.rand(K, B, N, generator=gen(34))
     else:
         # a point well inside the simplex: d log_prob / d x of Concrete grows like 1 / x, and the largest absolute difference
         # over elements ten orders of magnitude apart (a relaxed draw at this temperature has x down to e^-30) would compare
         # the rounding of one element only
-        v = torch.log_softmax(torch.randn(K, B, N, generator=torch.Generator().manual_seed(34)), -1)
+        v = torch.log_softmax(torch.randn(K, B, N, generator=gen(34)), -1)
         v = v if cls is ExpConcrete else torch.exp(v)
 
     def run(dtype, dev, dist_of):
@@ -278,15 +274,11 @@ def test_gradients_against_float64_autograd(cdev, cls):
     t64 = run(F64, "cpu", lambda l, x: torch_log_prob(cls, l, x, tau, weights=True))
     t32 = run(F32, "cpu", lambda l, x: torch_log_prob(cls, l, x, tau, weights=True))
     got = run(F32, cdev, lambda l, x: make(cls, l, tau=tau).log_prob(x))
-    for a, b, c in zip(got, t32, t64):
-        dist = float((b.double() - c).abs().max())
-        err = float((a.cpu().double() - c).abs().max())
-        print("%s: gradient error %.3e, torch's own float32 distance %.3e" % (cls.__name__, err, dist))
-        assert err <= 16 * dist, (cls.__name__, err, dist)
+    held_to_the_rule(cls.__name__, zip(("d/dlogits", "d/dvalue"), got, t32, t64))
 
     if cls in (ExpConcrete, Concrete):
         # the relaxed draw and its log-density: d (sum gz z + sum g lp) / d logits
-        gz = torch.randn(K, B, N, generator=torch.Generator().manual_seed(35))
+        gz = torch.randn(K, B, N, generator=gen(35))
 
         def truth(dtype):
             l0 = lg.to(dtype).requires_grad_(True)
@@ -301,10 +293,7 @@ def test_gradients_against_float64_autograd(cdev, cls):
             z = d.sample(K)
         lp = d.log_prob(z)
         got, = torch.autograd.grad((gz.to(cdev) * z).sum() + (g.to(cdev) * lp).sum(), [l0])
-        c, b = truth(F64), truth(F32)
-        dist = float((b.double() - c).abs().max())
-        err = float((got.cpu().double() - c).abs().max())
-        assert err <= 16 * dist, (cls.__name__, "draw", err, dist)
+        held_to_the_rule(cls.__name__, [("draw", got, truth(F32), truth(F64))])
         # is_reparameterized=False: the draw is a constant, the density keeps its direct dependence on logits
         l1 = lg.to(cdev).requires_grad_(True)
         d = make(cls, l1, tau=tau, is_reparameterized=False)
@@ -325,8 +314,8 @@ def test_gradcheck_of_the_float64_functions(N):
     K, R, tau = 2, 3, 0.8
     lg = rand_logits((R, N), 40 + N, dev, F64).requires_grad_(True)
     u = rand_u((K, R, N), 41 + N, F64).to(dev)
-    idx = torch.randint(0, N, (K, R), generator=torch.Generator().manual_seed(42)).to(dev)
-    x = torch.rand(K, R, N, dtype=F64, generator=torch.Generator().manual_seed(43)).to(dev).requires_grad_(True)
+    idx = torch.randint(0, N, (K, R), generator=gen(42)).to(dev)
+    x = torch.rand(K, R, N, dtype=F64, generator=gen(43)).to(dev).requires_grad_(True)
     y = cat_host.reference_relaxed_y(lg.detach().cpu(), u.cpu(), tau).to(dev).requires_grad_(True)
     kw = dict(eps=1e-6, atol=1e-6, rtol=1e-5, nondet_tol=0.0)
     assert torch.autograd.gradcheck(lambda l: F.CatSampleLogProb.apply(l, u, 0, 0, None, K, True)[2], (lg,), **kw)
@@ -340,38 +329,31 @@ def test_gradcheck_of_the_float64_functions(N):
 
 # ------------------------------------------------------------------------------------------------ launches and streams
 @pytest.mark.parametrize("cls", FAMILIES)
-def test_own_draw_then_log_prob_is_one_launch_each_way(cls):
-    """Counted through the host back-end's call record."""
-    import conftest
-    dev = torch.device("cpu")
-    host_backend.install(conftest.host_kernel_library())
-    cat_host.install()
-    try:
-        lg = rand_logits((4, 3, 6), 50, dev).requires_grad_(True)
-        del cat_host.calls[:]
+def test_own_draw_then_log_prob_is_one_launch_each_way(cdev, cls):
+    """Counted through the record of the binding's calls, on both back-ends."""
+    with cat_host.recording() as calls:
+        lg = rand_logits((4, 3, 6), 50, cdev).requires_grad_(True)
         d = make(cls, lg, group_ndims=1)
         z = d.sample(5)
         lp = d.log_prob(z)
         lp0 = d._log_prob_sum(None, 0)
         assert tuple(lp.shape) == (5, 4) and tuple(lp0.shape) == (5, 4, 3)
-        assert len(cat_host.calls) == 1 and cat_host.calls[0][0] in ("sample_logprob", "relaxed_sample_logprob")
+        assert len(calls) == 1 and calls[0].name in ("sample_logprob", "relaxed_sample_logprob")
         (lp.sum() + (z.sum() if z.requires_grad else 0.0)).backward()
-        assert len(cat_host.calls) == 2 and cat_host.calls[1][0] in ("logprob_bwd", "relaxed_sample_logprob_bwd")
+        assert len(calls) == 2 and calls[1].name in ("logprob_bwd", "relaxed_sample_logprob_bwd")
         assert "one launch" in zs.explain(d) and zs.explain(d).startswith(("C1", "C3")) and d.last_path["why"] is None
         d.log_prob(z.detach().clone())
-        assert len(cat_host.calls) == 3 and cat_host.calls[2][0] in ("logprob", "relaxed_logprob") and zs.explain(d).startswith(("C2", "C4"))
+        assert len(calls) == 3 and calls[2].name in ("logprob", "relaxed_logprob") and zs.explain(d).startswith(("C2", "C4"))
         # an output that never entered the loss costs no backward launch and no dense zero gradient
-        n = len(cat_host.calls)
+        n = len(calls)
         d2 = make(cls, lg)
         z2 = d2.sample(3)
         if z2.requires_grad:
             (z2 * z2).sum().backward()          # the draw alone: the log-density brings no gradient
-            assert len(cat_host.calls) == n + 2 and cat_host.calls[-1][0] == "relaxed_sample_logprob_bwd"
+            assert len(calls) == n + 2 and calls[-1].name == "relaxed_sample_logprob_bwd"
         else:
-            assert d2.log_prob(z2).sum().requires_grad and len(cat_host.calls) == n + 1
-    finally:
-        cat_host.uninstall()
-        host_backend.uninstall()
+            assert d2.log_prob(z2).sum().requires_grad and len(calls) == n + 1
+    print("launches on %s: %s" % (cdev.type, [c.name for c in calls]))
 
 
 @pytest.mark.parametrize("cls", FAMILIES)
@@ -545,8 +527,8 @@ def old_reduction_plan_of(self, x, dist, g):
 def test_pre_existing_families_are_bit_identical_with_the_old_reduction_plan(cdev, monkeypatch):
     from zhusuan.framework.stochastic_tensor import StochasticTensor
     mean = rand_logits((3, 4, 6), 90, cdev).requires_grad_(True)
-    eps = [torch.randn(5, 3, 4, 6, generator=torch.Generator().manual_seed(91)), rand_u((5, 3, 4, 6), 93)]
-    x = (torch.rand(3, 4, 6, generator=torch.Generator().manual_seed(92)) < 0.5).float().to(cdev)
+    eps = [torch.randn(5, 3, 4, 6, generator=gen(91)), rand_u((5, 3, 4, 6), 93)]
+    x = (torch.rand(3, 4, 6, generator=gen(92)) < 0.5).float().to(cdev)
 
     def build(net):
         z = net.normal('z', mean=mean, std=torch.ones_like(mean), n_samples=5, reduce_sum_dims=[3], reduce_mean_dims=[1])
@@ -573,7 +555,7 @@ OB, OK_, OD, ON, OX, OTAU = 3, 5, 2, 4, 6, 0.6
 
 
 def objective_setup(dev, dtype):
-    g = torch.Generator().manual_seed(100)
+    g = gen(100)
     P = dict(enc=0.7 * torch.randn(OX, OD * ON, generator=g, dtype=F64), dec=0.7 * torch.randn(OD * ON, OX, generator=g, dtype=F64),
              bias=0.3 * torch.randn(OX, generator=g, dtype=F64))
     P = {k: v.to(dtype).to(dev).requires_grad_(True) for k, v in P.items()}
@@ -652,9 +634,4 @@ def test_objectives_over_categorical_latents(cdev, mode):
     pairs = [("loss", loss, l32, l64)] + [(n, a, b, c) for n, a, b, c in zip(P.keys(), grads, g32, g64)]
     for name, a, b, c in pairs:
         assert (a is None) == (c is None), name
-        if a is None:
-            continue
-        dist = float((b.detach().cpu().double() - c.detach().cpu()).abs().max())
-        err = float((a.detach().cpu().double() - c.detach().cpu()).abs().max())
-        print("%s %s: error %.3e, the torch model's float32 distance %.3e" % (mode, name, err, dist))
-        assert err <= 16 * dist, (mode, name, err, dist)
+    held_to_the_rule(mode, [p for p in pairs if p[1] is not None])

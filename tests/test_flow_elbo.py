@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import flow_host
+import truth
 from flow_host import fdev  # noqa: F401
 
 B, X, Z, H = 4, 6, 5, 8
@@ -30,7 +31,7 @@ def build(method, dev, estimator="sgvb", seed=0):
 
 
 def data(dev):
-    g = torch.Generator().manual_seed(9)
+    g = truth.gen(9)
     x = (torch.rand(B, X, generator=g) < 0.5).float().to(dev)
     eps = [torch.randn(B, Z, generator=g).to(dev) for _ in range(2)]
     return x, eps

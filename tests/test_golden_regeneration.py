@@ -8,12 +8,10 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 from conftest import GOLDEN
-
-REF = "/root/reference"
+from reference_runs import REF, same_fixtures
 
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "zhusuan")), reason="reference checkout not present")
@@ -29,16 +27,4 @@ def test_goldens_regenerate_bit_identically(tmp_path):
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
     r = subprocess.run([sys.executable, "-c", code], cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
-    made = sorted(f for f in os.listdir(tmp_path) if f.endswith(".npz"))
-    committed = sorted(f for f in os.listdir(GOLDEN) if f.endswith(".npz"))
-    assert made == committed
-    n = 0
-    for f in made:
-        a, b = np.load(os.path.join(tmp_path, f)), np.load(os.path.join(GOLDEN, f))
-        assert sorted(a.files) == sorted(b.files), f
-        for k in a.files:
-            x, y = a[k], b[k]
-            assert x.shape == y.shape and x.dtype == y.dtype, (f, k)
-            assert np.array_equal(x, y, equal_nan=(x.dtype.kind in "fc")), (f, k)
-            n += 1
-    assert n > 2500
+    assert same_fixtures(str(tmp_path), GOLDEN, equal_nan=True) > 2500

@@ -24,8 +24,7 @@ import pytest
 import torch
 import torch.nn as nn
 
-import host_backend
-from conftest import host_kernel_library
+import host_routing
 from flow_host import fdev  # noqa: F401  (fixture)
 import flow_host
 
@@ -727,13 +726,8 @@ def _evaluate(make, dtype, dev):
 
 
 def _on_host(make, dtype):
-    host_backend.install(host_kernel_library())
-    flow_host.install()
-    try:
-        return _evaluate(make, dtype, torch.device("cpu"))
-    finally:
-        flow_host.uninstall()
-        host_backend.uninstall()
+    with host_routing.host(flow_host.router) as dev:
+        return _evaluate(make, dtype, dev)
 
 
 def twin_check(function, make, ran32=()):

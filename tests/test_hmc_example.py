@@ -3,7 +3,9 @@ import math
 
 import torch
 
+import hmc_host
 import host_backend
+import host_routing
 from hmc_host import hdev  # noqa: F401
 
 
@@ -19,17 +21,10 @@ def test_example_runs_at_a_tiny_size(hdev):
 
 def test_example_runs_with_the_reference_examples_default_sizes_on_the_host():
     """n_x = 1, one chain, 200 iterations, 20 leapfrog steps: the reference example's parameter block."""
-    import conftest
-    import hmc_host
     from examples import gaussian_hmc
-    host_backend.install(conftest.host_kernel_library())
-    hmc_host.install()
-    try:
+    with host_routing.host(hmc_host.router):
         host_backend.manual_seed(1)
         r = gaussian_hmc.run(device="cpu")
-    finally:
-        hmc_host.uninstall()
-        host_backend.uninstall()
     assert tuple(r["samples"].shape) == (100, 1, 1) and bool(torch.isfinite(r["samples"]).all())
     # 100 correlated draws of one chain: a loose sanity band around the unit standard deviation, not a test of the sampler
     assert 0.3 < float(r["std"]) < 3.0 and abs(float(r["mean"])) < 1.5 and r["acceptance"] > 0.3

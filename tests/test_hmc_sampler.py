@@ -10,17 +10,11 @@ import torch
 
 import hmc_host
 import host_backend
+import truth
 from hmc_host import hdev  # noqa: F401
+from truth import seed_all
 
 F32, F64 = torch.float32, torch.float64
-
-
-def seed_all(dev, s):
-    torch.manual_seed(s)
-    if dev.type == "cpu":
-        host_backend.manual_seed(s)
-    else:
-        torch.cuda.manual_seed(s)
 
 
 # ------------------------------------------------------------------------------------------------ models
@@ -52,7 +46,7 @@ N_DATA = 6
 
 
 def blr_data(C, dtype=F32):
-    gen = torch.Generator().manual_seed(40)
+    gen = truth.gen(40)
     x = torch.randn(N_DATA, 5, generator=gen, dtype=F64)
     y = (x.sum(1) * 0.3 + 0.2 * torch.randn(N_DATA, generator=gen, dtype=F64))
     return x.to(dtype), y.to(dtype).unsqueeze(0).expand(C, N_DATA).contiguous()
@@ -177,7 +171,7 @@ def test_info_fields_shapes_inplace_and_chain_shape_error(hdev, chain_shape):
     from zhusuan.mcmc import HMC
     std = torch.tensor([0.5, 1.0, 2.0])
     net = gaussian(hdev, std)
-    seed_all(hdev, 1)
+    seed_all(1, hdev)
     x = torch.randn(*chain_shape, 3).to(hdev)
     kept = x.clone()
     h = HMC(step_size=0.2, n_leapfrogs=3)
@@ -198,9 +192,9 @@ def test_info_fields_shapes_inplace_and_chain_shape_error(hdev, chain_shape):
     # in place: the same objects, written into their storage
     y = x.clone()
     ptr = y.data_ptr()
-    seed_all(hdev, 2)
+    seed_all(2, hdev)
     s2, _ = h.sample(net, {}, {'x': y}, inplace=True)
-    seed_all(hdev, 2)
+    seed_all(2, hdev)
     s3, _ = h.sample(net, {}, {'x': x})
     assert s2['x'] is y and y.data_ptr() == ptr and torch.equal(y, s3['x']) and h.t == 3
     with pytest.raises(ValueError, match="'x' is not contiguous"):
@@ -218,7 +212,7 @@ L_TRAJ, EPS_TRAJ, ITERS = 3, 0.05, 4
 
 
 def trajectory_inputs(C, seed):
-    gen = torch.Generator().manual_seed(seed)
+    gen = truth.gen(seed)
     q0 = [0.3 * torch.randn(C, 5, generator=gen), 0.3 * torch.randn(C, 2, 3, generator=gen)]
     zs = [[torch.randn(C, 5, generator=gen), torch.randn(C, 2, 3, generator=gen)] for _ in range(ITERS)]
     us = [torch.rand(C, generator=gen) for _ in range(ITERS)]
@@ -286,7 +280,7 @@ def test_launch_budget_and_call_ids(hdev, L):
     obs = {'x': x.to(hdev), 'y': y.to(hdev)}
     latent = {'w': torch.zeros(C, 5, device=hdev), 'b': torch.zeros(C, 2, 3, device=hdev)}
     h = HMC(step_size=0.05, n_leapfrogs=L)
-    seed_all(hdev, 3)
+    seed_all(3, hdev)
     for it in range(2):
         with Counted(net) as c:
             latent, _ = h.sample(net, obs, latent)
@@ -308,7 +302,7 @@ def test_forty_latents_are_two_chunks_and_one_decide(hdev, dtype):
     from zhusuan.mcmc import HMC
     k, C, L, eps = 40, 3, 3, 0.3
     net = independent_normals(hdev, k, C, dtype)
-    gen = torch.Generator().manual_seed(8)
+    gen = truth.gen(8)
     shapes = [(C, 1 + i % 5) for i in range(k)]
     q0 = [torch.randn(s, generator=gen, dtype=F64).to(dtype) for s in shapes]
     z = [torch.randn(s, generator=gen, dtype=F64).to(dtype) for s in shapes]
@@ -369,7 +363,7 @@ def test_reversibility_through_the_move_entry_points(hdev, dtype):
     from zhusuan import _hmc_hip
     C, D, L, eps = 5, 7, 10, 0.1
     std = torch.linspace(0.5, 2.0, D, dtype=F64).to(dtype).to(hdev)
-    gen = torch.Generator().manual_seed(2)
+    gen = truth.gen(2)
     q0 = (torch.randn(C, D, generator=gen, dtype=F64) * std.cpu().double()).to(dtype).to(hdev)
     z = torch.randn(C, D, generator=gen, dtype=F64).to(dtype).to(hdev)
     state = torch.tensor([eps, eps, 0, 0, 0, 0, 0, 0], dtype=F64, device=hdev)
@@ -400,7 +394,7 @@ def test_energy_error_is_second_order(hdev):
     C, D = 65, 7
     std = torch.linspace(0.5, 2.0, D, dtype=F64)
     net = gaussian(hdev, std)
-    gen = torch.Generator().manual_seed(6)
+    gen = truth.gen(6)
     q0 = (torch.randn(C, D, generator=gen, dtype=F64) * std).to(hdev)
     z = torch.randn(C, D, generator=gen, dtype=F64)
     u = torch.rand(C, generator=gen, dtype=F64)
@@ -435,7 +429,7 @@ def test_samples_the_reference_tests_density(hdev, dtype):
     net = quartic(hdev)
     x = torch.zeros(n, dtype=dtype, device=hdev)
     sampler = HMC(step_size=0.1, n_leapfrogs=10)
-    seed_all(hdev, 3)
+    seed_all(3, hdev)
     rate = 0.0
     for _ in range(100):
         info = sampler.sample(net, {}, {'x': x}, inplace=True)[1]
@@ -459,7 +453,7 @@ def test_step_size_adaptation_from_both_sides(hdev):
     net = gaussian(hdev, std)
     frozen, rates, first_rates = [], [], []
     for e0 in (0.01, 5.0):
-        seed_all(hdev, 5)
+        seed_all(5, hdev)
         h = HMC(step_size=e0, n_leapfrogs=5, adapt_step_size=True)
         latent = {'x': torch.zeros(256, 10, dtype=F64, device=hdev)}
         for it in range(300):
@@ -491,7 +485,7 @@ def test_non_finite_energies_reject_only_their_chain(hdev):
     x[5], x[9] = 1e20, 3e9
     kept = x.clone()
     h = HMC(step_size=0.1, n_leapfrogs=4, adapt_step_size=True)
-    seed_all(hdev, 9)
+    seed_all(9, hdev)
     for _ in range(5):
         _, info = h.sample(net, {}, {'x': x}, inplace=True)
         assert float(info.acceptance_rate[5]) == 0.0 and float(info.acceptance_rate[9]) == 0.0

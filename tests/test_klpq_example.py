@@ -9,24 +9,15 @@ import torch
 
 import cat_host
 import host_backend
+import host_routing
+import klpq_host
 import zhusuan as zs
-from klpq_host import kdev  # noqa: F401
 
 TINY = dict(x_dim=16, h1=8, h2=4, n_latents=2, n_categories=4, n_samples=5)
 
 
-@pytest.fixture
-def edev(kdev):
-    """``kdev`` with the categorical binding routed as well (the example's one-hot latent)."""
-    if kdev.type == "cpu":
-        cat_host.install()
-        try:
-            yield kdev
-        finally:
-            cat_host.uninstall()
-    else:
-        cat_host.uninstall()
-        yield kdev
+# ``kdev`` with the categorical binding routed as well (the example's one-hot latent)
+edev = host_routing.dev_fixture("edev", klpq_host.router, cat_host.router)
 
 
 def run(dev, steps, **kw):

@@ -15,29 +15,17 @@ from zhusuan.variational import InclusiveKLObjective, KLpq
 
 import cat_host
 import host_backend
+import host_routing
 import klpq_host
+import truth
 from klpq_host import kdev  # noqa: F401
+from truth import held_to_the_rule, seed_all
 
 F32, F64 = torch.float32, torch.float64
 
 
-@pytest.fixture
-def qdev(kdev):
-    """``kdev`` with the categorical binding routed as well (the model has an onehot_categorical latent)."""
-    if kdev.type == "cpu":
-        cat_host.install()
-        try:
-            yield kdev
-        finally:
-            cat_host.uninstall()
-    else:
-        cat_host.uninstall()
-        yield kdev
-
-
-def seed_all(s):
-    torch.manual_seed(s)
-    host_backend.manual_seed(s)
+# ``kdev`` with the categorical binding routed as well (the model has an onehot_categorical latent)
+qdev = host_routing.dev_fixture("qdev", klpq_host.router, cat_host.router)
 
 
 class Net(BayesianNet):
@@ -94,7 +82,7 @@ MB, MK, MH, MN, MX = 3, 5, 4, 4, 6
 
 
 def setup(dev, dtype):
-    g = torch.Generator().manual_seed(300)
+    g = truth.gen(300)
     shapes = dict(qh=(MX, MH), qz=(MX, MN), pz=(MN,), ph=(MN, MH), bh=(MH,), pxh=(MH, MX), pxz=(MN, MX), bx=(MX,))
     P = {k: (0.7 * torch.randn(s, generator=g, dtype=F64)).to(dtype).to(dev).requires_grad_(True) for k, s in shapes.items()}
     x = (torch.rand(MB, MX, generator=g) < 0.5).to(dtype).to(dev)
@@ -148,18 +136,6 @@ def torch_model(dtype, x, draws, model_grad):
     cost, bound, ess = torch_klpq(*torch_terms(P, x, draws, dtype), model_grad)
     loss = cost.mean()
     return loss, torch.autograd.grad(loss, list(P.values()), allow_unused=True), cost, bound, ess
-
-
-def held_to_the_rule(tag, pairs):
-    """every (name, got, float32 torch, float64 torch): |got - f64| <= 16 x |f32 - f64|, the suite's rule"""
-    worst = 0.0
-    for name, a, b, c in pairs:
-        dist = float((b.detach().cpu().double() - c.detach().cpu()).abs().max())
-        err = float((a.detach().cpu().double() - c.detach().cpu()).abs().max())
-        print("%s %s: error %.3e, the torch model's float32 distance %.3e (%.2f x)" % (tag, name, err, dist, err / dist if dist else 0.0))
-        worst = max(worst, err / dist if dist else (0.0 if err == 0 else math.inf))
-        assert err <= 16 * dist, (tag, name, err, dist)
-    print("%s: worst multiple %.2f" % (tag, worst))
 
 
 @pytest.mark.parametrize("model_grad", [False, True])
@@ -243,44 +219,42 @@ def test_a_reparameterised_latent_raises_and_a_single_sample_warns_once(qdev):
 
 
 # ------------------------------------------------------------------------------------------------ paths and launches
-def test_one_launch_each_way_and_none_for_an_unused_cost():
-    dev = torch.device("cpu")
-    host_backend.install(__import__("conftest").host_kernel_library())
-    klpq_host.install()
-    cat_host.install()
-    try:
-        P, x = setup(dev, F32)
-        gen, var = nets(P, dev)
-        obj = KLpq(gen, var, axis=0, model_grad=True)
-        del klpq_host.calls[:]
+def launch(c):
+    """(K, B, terms of p, terms of q, flags) of a recorded forward; for a backward the terms are those that ask for a gradient"""
+    if c.name == "forward":
+        (terms_p, terms_q, K, B), flags = c.args, dict(dict(model_grad=False, bound_only=False, want_mean=False), **c.kwargs)
+        return K, B, len(terms_p), len(terms_q), flags
+    (_, _, want_p, want_q, K, B), flags = c.args[:6], dict(dict(model_grad=False, gcost_is_mean=False), **c.kwargs)
+    return K, B, sum(map(bool, want_p)), sum(map(bool, want_q)), flags
+
+
+def test_one_launch_each_way_and_none_for_an_unused_cost(qdev):
+    P, x = setup(qdev, F32)
+    gen, var = nets(P, qdev)
+    obj = KLpq(gen, var, axis=0, model_grad=True).to(qdev)
+    with klpq_host.recording() as calls:
         loss = obj({'x': x})
-        assert [c[0] for c in klpq_host.calls] == ["forward"] and klpq_host.calls[0][1:5] == (MK, MB, 3, 2)
-        assert klpq_host.calls[0][5] == dict(model_grad=True, bound_only=False, want_mean=True)
+        assert [c.name for c in calls] == ["forward"] and launch(calls[0])[:4] == (MK, MB, 3, 2)
+        assert launch(calls[0])[4] == dict(model_grad=True, bound_only=False, want_mean=True)
         loss.backward()
-        assert [c[0] for c in klpq_host.calls] == ["forward", "backward"]
-        assert klpq_host.calls[1][3:5] == (3, 2) and klpq_host.calls[1][5] == dict(model_grad=True, gcost_is_mean=True)
+        assert [c.name for c in calls] == ["forward", "backward"]
+        assert launch(calls[1])[2:4] == (3, 2) and launch(calls[1])[4] == dict(model_grad=True, gcost_is_mean=True)
         # without model_grad the generator's terms ask for no gradient
-        obj = KLpq(gen, var, axis=0)
-        del klpq_host.calls[:]
+        obj = KLpq(gen, var, axis=0).to(qdev)
         obj({'x': x}).backward()
-        assert [c[0] for c in klpq_host.calls] == ["forward", "backward"] and klpq_host.calls[1][3:5] == (0, 2)
+        assert [c.name for c in calls[2:]] == ["forward", "backward"] and launch(calls[3])[2:4] == (0, 2)
         # a cost that did not enter the loss costs no backward launch
-        del klpq_host.calls[:]
         obj({'x': x})
         (obj.last_ess.sum() + obj.last_iw_bound.sum() + P['qh'].sum()).backward()
-        assert [c[0] for c in klpq_host.calls] == ["forward"]
+        assert [c.name for c in calls[4:]] == ["forward"]
         # is_loglikelihood: one launch in the bound-only mode
-        del klpq_host.calls[:]
         zs.is_loglikelihood(gen, var, {'x': x})
-        assert [c[0] for c in klpq_host.calls] == ["forward"] and klpq_host.calls[0][5]["bound_only"]
-    finally:
-        cat_host.uninstall()
-        klpq_host.uninstall()
-        host_backend.uninstall()
+        assert [c.name for c in calls[5:]] == ["forward"] and launch(calls[5])[4]["bound_only"]
+    print("launches on %s: %s" % (qdev.type, [(c.name,) + launch(c) for c in calls]))
 
 
 def rand_terms(dev, shapes, seed, dtype=F32):
-    g = torch.Generator().manual_seed(seed)
+    g = truth.gen(seed)
     return [(1.5 * torch.randn(s, generator=g, dtype=F64) - 1.0).to(dtype).to(dev).requires_grad_(True) for s in shapes]
 
 
@@ -459,7 +433,7 @@ def test_gradcheck_of_the_f64_function(K, B, model_grad, want_mean):
     from zhusuan.variational._klpq_functions import InclusiveKL
     klpq_host.uninstall()
     dev = torch.device("cuda:0")
-    g = torch.Generator().manual_seed(K + B)
+    g = truth.gen(K + B)
     tp = [torch.randn(K, B, generator=g, dtype=F64).to(dev).requires_grad_(True), torch.randn(B, K, generator=g, dtype=F64).to(dev).requires_grad_(True)]
     tq = [torch.randn(K, B, generator=g, dtype=F64).to(dev).requires_grad_(True), torch.randn(1, B, generator=g, dtype=F64).to(dev).requires_grad_(True)]
 

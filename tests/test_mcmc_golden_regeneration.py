@@ -5,12 +5,11 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from reference_runs import REF, same_fixtures
 
-REF = "/root/reference"
 MCMC = os.path.join(GOLDEN, "mcmc")
 
 
@@ -20,16 +19,5 @@ def test_mcmc_goldens_regenerate_bit_identically(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(MCMC, "gen_mcmc_golden.py"), "--ref", REF, "--out", str(tmp_path)],
                        cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
-    made = sorted(f for f in os.listdir(tmp_path) if f.endswith(".npz"))
-    committed = sorted(f for f in os.listdir(MCMC) if f.endswith(".npz"))
-    assert made == committed and len(made) == 4
-    n = 0
-    for f in made:
-        a, b = np.load(os.path.join(tmp_path, f)), np.load(os.path.join(MCMC, f))
-        assert sorted(a.files) == sorted(b.files), f
-        for k in a.files:
-            x, y = a[k], b[k]
-            assert x.shape == y.shape and x.dtype == y.dtype, (f, k)
-            assert np.array_equal(x, y), (f, k)
-            n += 1
-    assert n > 100
+    assert same_fixtures(str(tmp_path), MCMC) > 100
+    assert len([f for f in os.listdir(MCMC) if f.endswith(".npz")]) == 4

@@ -13,15 +13,9 @@ import torch
 import host_backend
 import mcmc_models as M
 from conftest import PKG_ROOT
+import truth
 from mcmc_host import mdev  # noqa: F401
-
-
-def seed_all(dev, s):
-    torch.manual_seed(s)
-    if dev.type == "cpu":
-        host_backend.manual_seed(s)
-    else:
-        torch.cuda.manual_seed(s)
+from truth import seed_all
 
 
 def bnn(dev, layers=(3, 4, 1)):
@@ -104,7 +98,7 @@ def test_import_zhusuan_does_not_load_the_sampler_binding():
 def test_resample_step_and_aliasing(mdev, name):
     make = dict(samplers())[name]
     net, obs = bnn(mdev)
-    seed_all(mdev, 4)
+    seed_all(4, mdev)
     a = make()
     first = a.sample(net, obs, resample=True)
     assert a.t == 1 and list(first.keys()) == ['w0', 'w1'] and a.device == mdev
@@ -118,7 +112,7 @@ def test_resample_step_and_aliasing(mdev, name):
         assert torch.equal(first[k].detach(), kept[k]) and out3[k].data_ptr() != first[k].data_ptr()
         assert out3[k].is_leaf and out3[k].requires_grad and bool(torch.isfinite(out3[k]).all())
         assert not torch.equal(out3[k].detach(), kept[k])
-    seed_all(mdev, 4)
+    seed_all(4, mdev)
     b = make()
     again = b.sample(net, obs, resample=True)
     outs = [b.sample(net, obs) for _ in range(3)]
@@ -136,7 +130,7 @@ def test_an_observed_latent_is_not_updated(mdev):
     w1 = torch.full((3, 1, 5), 0.25, device=mdev)
     obs = dict(obs, w1=w1)
     s = SGLD(1e-3)
-    seed_all(mdev, 1)
+    seed_all(1, mdev)
     first = s.sample(net, obs, resample=True)
     assert list(first.keys()) == ['w0']
     with Counted() as c:
@@ -151,7 +145,7 @@ def test_launches_per_step(mdev, name):
     make = dict(samplers())[name]
     net, obs = bnn(mdev)
     s = make()
-    seed_all(mdev, 2)
+    seed_all(2, mdev)
     s.sample(net, obs, resample=True)
     for t in range(1, 5):
         with Counted() as c:
@@ -176,7 +170,7 @@ def test_forty_latents_split_across_two_launches(mdev, dtype):
     from zhusuan.mcmc import SGLD
     k, lr = 40, 1e-2
     net = independent_normals(mdev, k, dtype)
-    gen = torch.Generator().manual_seed(8)
+    gen = truth.gen(8)
     shapes = [(1 + i % 5,) for i in range(k)]
     prior = [torch.randn(s, generator=gen, dtype=torch.float64).to(dtype) for s in shapes * 2]
     noise = [torch.randn(s, generator=gen, dtype=torch.float64).to(dtype) for s in shapes]
@@ -201,7 +195,7 @@ def test_forty_latents_split_across_two_launches(mdev, dtype):
 def test_example_runs_three_steps(mdev):
     from examples import bnn_sgmcmc
     for name in ("sgld", "sghmc"):
-        seed_all(mdev, 0)
+        seed_all(0, mdev)
         rmse = bnn_sgmcmc.run(steps=3, batch=8, particles=2, layer_sizes=(3, 4, 1), sampler=name, device=mdev, n_train=16, n_test=8)
         assert isinstance(rmse, float) and math.isfinite(rmse) and rmse > 0
 

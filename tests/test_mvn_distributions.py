@@ -15,19 +15,12 @@ from zhusuan.variational.elbo import ELBO
 from zhusuan.variational.importance_weighted_objective import ImportanceWeightedObjective
 
 import host_backend
+import host_routing
 import mvn_host
 from mvn_host import vdev  # noqa: F401
+from truth import gen, held_to_the_rule, seed_all
 
 F32, F64 = torch.float32, torch.float64
-
-
-def seed_all(s):
-    torch.manual_seed(s)
-    host_backend.manual_seed(s)
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
 
 
 def rand_mean(shape, seed, dev="cpu", dtype=F32):
@@ -149,11 +142,10 @@ def test_given_values_broadcast_against_the_batch_shape(vdev):
     # few rows and many observations: presented to the kernels as rows of one particle
     d1 = MVN(rand_mean((4,), 12, vdev), rand_tril((), 4, 13, vdev))
     v = torch.randn(40, 4, generator=gen(14))
-    del mvn_host.calls[:]
     want = torch_mvn(d1.mean.cpu().double(), d1.cov_tril.cpu().double()).log_prob(v.double())
-    assert float((d1.log_prob(v.to(vdev)).cpu().double() - want).abs().max()) < 1e-4
-    if vdev.type == "cpu":
-        assert [(c[0], c[1], c[2]) for c in mvn_host.calls] == [("logprob", 1, (40, 4, 4))]
+    with mvn_host.recording() as calls:
+        assert float((d1.log_prob(v.to(vdev)).cpu().double() - want).abs().max()) < 1e-4
+    assert [(c.name, c.args[2], c.args[1]) for c in calls] == [("logprob", 1, (40, 4, 4))]          # (name, K, cov_tril's shape)
 
 
 def test_the_upper_triangle_is_not_read(vdev):
@@ -205,12 +197,7 @@ def unpack_lower(flat, D):
 
 
 def _check_grads(name, got, t32, t64):
-    for what, a, b, c in zip(("mean", "cov_tril", "value"), got, t32, t64):
-        dist = float((b.double() - c).abs().max())
-        err = float((a.cpu().double() - c).abs().max())
-        GRAD_WORST[(name, what)] = err / dist if dist > 0 else 0.0
-        print("%s d/d%s: error %.3e, torch's own float32 distance %.3e (x %.2f)" % (name, what, err, dist, err / max(dist, 1e-300)))
-        assert err <= 16 * dist, (name, what, err, dist)
+    held_to_the_rule(name, zip(("d/dmean", "d/dcov_tril", "d/dvalue"), got, t32, t64), GRAD_WORST)
 
 
 @pytest.mark.parametrize("D", [1, 3, 10])
@@ -287,45 +274,38 @@ def test_gradcheck_of_the_float64_functions(D):
 
 
 # ------------------------------------------------------------------------------------------------ launches and streams
-def test_own_draw_then_log_prob_is_one_launch_each_way():
-    """Counted through the host back-end's call record."""
-    import conftest
-    dev = torch.device("cpu")
-    host_backend.install(conftest.host_kernel_library())
-    mvn_host.install()
-    try:
-        mean = rand_mean((4, 3, 6), 90, dev).requires_grad_(True)
-        tril = rand_tril((4, 3), 6, 91, dev).requires_grad_(True)
-        del mvn_host.calls[:]
+def test_own_draw_then_log_prob_is_one_launch_each_way(vdev):
+    """Counted through the record of the binding's calls, on both back-ends."""
+    with mvn_host.recording() as calls:
+        mean = rand_mean((4, 3, 6), 90, vdev).requires_grad_(True)
+        tril = rand_tril((4, 3), 6, 91, vdev).requires_grad_(True)
         d = MVN(mean, tril, group_ndims=1)
         z = d.sample(5)
         lp = d.log_prob(z)
         lp0 = d._log_prob_sum(None, 0)
         assert tuple(lp.shape) == (5, 4) and tuple(lp0.shape) == (5, 4, 3)
-        assert [c[0] for c in mvn_host.calls] == ["sample_logprob"]
+        assert [c.name for c in calls] == ["sample_logprob"]
         (lp.sum() + z.sum()).backward()
-        assert [c[0] for c in mvn_host.calls] == ["sample_logprob", "sample_logprob_bwd"]
-        assert mvn_host.calls[0][3] == mvn_host.calls[1][3]          # the backward regenerates the forward's noise
+        assert [c.name for c in calls] == ["sample_logprob", "sample_logprob_bwd"]
+        assert calls[0].kwargs["call"] == calls[1].kwargs["call"]          # the backward regenerates the forward's noise
         assert zs.explain(d).startswith("V1") and "one launch" in zs.explain(d) and d.last_path["why"] is None
         d.log_prob(z.detach().clone())
-        assert [c[0] for c in mvn_host.calls][2:] == ["logprob"] and zs.explain(d).startswith("V2")
+        assert [c.name for c in calls][2:] == ["logprob"] and zs.explain(d).startswith("V2")
         # an output that never entered the loss costs no backward launch and no dense zero gradient
-        n = len(mvn_host.calls)
+        n = len(calls)
         d2 = MVN(mean, tril)
         z2 = d2.sample(3)
         (z2 * z2).sum().backward()          # the draw alone
-        assert len(mvn_host.calls) == n + 2 and mvn_host.calls[-1][0] == "sample_logprob_bwd"
+        assert len(calls) == n + 2 and calls[-1].name == "sample_logprob_bwd"
         d3 = MVN(mean, tril, is_reparameterized=False)
         z3 = d3.sample(3)
         assert not z3.requires_grad and d3.log_prob(z3).requires_grad
-        n = len(mvn_host.calls)
+        n = len(calls)
         d4 = MVN(mean.detach(), tril.detach())
-        x = torch.randn(3, 4, 3, 6, generator=gen(92)).requires_grad_(True)
+        x = torch.randn(3, 4, 3, 6, generator=gen(92)).to(vdev).requires_grad_(True)
         d4.log_prob(x).sum().backward()
-        assert [c[0] for c in mvn_host.calls][n:] == ["logprob", "logprob_bwd"] and x.grad is not None
-    finally:
-        mvn_host.uninstall()
-        host_backend.uninstall()
+        assert [c.name for c in calls][n:] == ["logprob", "logprob_bwd"] and x.grad is not None
+    print("launches on %s: %s" % (vdev.type, [c.name for c in calls]))
 
 
 def test_wide_rows_take_the_torch_composition(vdev):
@@ -333,18 +313,18 @@ def test_wide_rows_take_the_torch_composition(vdev):
     mean, tril = rand_mean((B, D), 100), rand_tril((B,), D, 101)
     eps = torch.randn(K, B, D, generator=gen(102))
     d = MVN(mean.to(vdev), tril.to(vdev))
-    del mvn_host.calls[:]
-    with zs.inject_epsilon([eps]):
-        z = d.sample(K)
-    assert "torch composition" in zs.explain(d) and "64" in d.last_path["why"]
-    lp = d.log_prob(z)
+    with mvn_host.recording() as calls:
+        with zs.inject_epsilon([eps]):
+            z = d.sample(K)
+        assert "torch composition" in zs.explain(d) and "64" in d.last_path["why"]
+        lp = d.log_prob(z)
+        x = mean[None] + torch.randn(K, B, D, generator=gen(103))
+        lp2 = d.log_prob(x.to(vdev))
+        assert "torch composition" in zs.explain(d) and "solve_triangular" in zs.explain(d)
+    assert calls == []
     tz, tlp = mvn_host.reference_sample(mean, tril, eps)
     assert float((z.cpu().double() - tz).abs().max()) < 1e-4 and float((lp.cpu().double() - tlp).abs().max()) < 1e-3
-    x = mean[None] + torch.randn(K, B, D, generator=gen(103))
-    lp2 = d.log_prob(x.to(vdev))
-    assert "torch composition" in zs.explain(d) and "solve_triangular" in zs.explain(d)
     assert float((lp2.cpu().double() - mvn_host.reference_logprob(mean, tril, x)).abs().max()) < 1e-3
-    assert mvn_host.calls == []
     # a detached wide draw keeps the density's direct dependence on the parameters (what the score-function estimators need)
     m0, t0 = mean.to(vdev).requires_grad_(True), tril.to(vdev).requires_grad_(True)
     dn = MVN(m0, t0, is_reparameterized=False)
@@ -399,27 +379,19 @@ class Net(BayesianNet):
 
 
 def test_two_nodes_of_one_net_receive_different_calls():
-    import conftest
-    dev = torch.device("cpu")
-    host_backend.install(conftest.host_kernel_library())
-    mvn_host.install()
-    try:
+    with host_routing.host(mvn_host.router) as dev, mvn_host.recording() as calls:
         mean, tril = rand_mean((3, 4), 120, dev), rand_tril((3,), 4, 121, dev)
 
         def build(net):
             net.multivariate_normal_cholesky('a', mean, tril, n_samples=2)
             net.multivariate_normal_cholesky('b', mean, tril, n_samples=2)
         seed_all(5)
-        del mvn_host.calls[:]
         net = Net(build)
         net({})
         a, b = net.nodes['a'].tensor, net.nodes['b'].tensor
-        ids = [c[3] for c in mvn_host.calls if c[0] == "sample_logprob"]
+        ids = [c.kwargs["call"] for c in calls if c.name == "sample_logprob"]
         # (the factory draws once and the read of .tensor draws again, as in the reference: four draws, four ids)
         assert len(ids) >= 2 and len(set(ids)) == len(ids) and not torch.equal(a, b)
-    finally:
-        mvn_host.uninstall()
-        host_backend.uninstall()
 
 
 @pytest.mark.gpu
@@ -586,9 +558,4 @@ def test_objectives_over_a_multivariate_normal_latent(vdev, mode):
     pairs = [("loss", loss, l32, l64)] + [(n, a, b, c) for n, a, b, c in zip(P.keys(), grads, g32, g64)]
     for name, a, b, c in pairs:
         assert (a is None) == (c is None), name
-        if a is None:
-            continue
-        dist = float((b.detach().cpu().double() - c.detach().cpu()).abs().max())
-        err = float((a.detach().cpu().double() - c.detach().cpu()).abs().max())
-        print("%s %s: error %.3e, the torch model's float32 distance %.3e" % (mode, name, err, dist))
-        assert err <= 16 * dist, (mode, name, err, dist)
+    held_to_the_rule(mode, [p for p in pairs if p[1] is not None])

@@ -16,13 +16,10 @@ import torch
 import host_backend
 import nf_host
 from nf_host import ndev  # noqa: F401
+from truth import gen, held_to_the_rule
 
 F32, F64 = torch.float32, torch.float64
 WORST = {}
-
-
-def gen(seed):
-    return torch.Generator().manual_seed(seed)
 
 
 # ------------------------------------------------------------------------------------------------ the example's op sequence
@@ -57,13 +54,7 @@ def grads_of(outs, cots, leaves):
 
 
 def check(name, got, t32, t64):
-    for what, a, b, c in zip(name[1], got, t32, t64):
-        dist = float((b.double() - c).abs().max())
-        err = float((a.detach().cpu().double() - c).abs().max())
-        mult = err / dist if dist > 0 else (0.0 if err == 0 else float("inf"))
-        WORST[(name[0], what)] = max(WORST.get((name[0], what), 0.0), mult)
-        print("%s %s: error %.3e, the sequence's own float32 distance %.3e (x %.2f)" % (name[0], what, err, dist, mult))
-        assert err <= 16 * dist, (name, what, err, dist)
+    held_to_the_rule(name[0], zip(name[1], got, t32, t64), WORST)
 
 
 # ------------------------------------------------------------------------------------------------ surface

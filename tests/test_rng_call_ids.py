@@ -16,6 +16,7 @@ import flow_host
 import helpers as H
 import hmc_host
 import host_backend
+import host_routing
 import mcmc_host
 import zhusuan as zs
 from zhusuan import _hip, _ops, _rng
@@ -27,22 +28,9 @@ SEED = 67280421310721 + 2 ** 40          # upper word non-zero, as every seed of
 STEPS = 3
 
 
-@pytest.fixture
-def adev(dev):
-    """The suite's ``dev`` with every sampler / flow binding routed like the main library."""
-    mods = (mcmc_host, hmc_host, flow_host)
-    if dev.type == "cpu":
-        for m in mods:
-            m.install()
-        try:
-            yield dev
-        finally:
-            for m in mods:
-                m.uninstall()
-    else:
-        for m in mods:
-            m.uninstall()
-        yield dev
+ROUTERS = (mcmc_host.router, hmc_host.router, flow_host.router)
+# the suite's ``dev`` with every sampler / flow binding routed like the main library
+adev = host_routing.dev_fixture("adev", *ROUTERS)
 
 
 # ------------------------------------------------------------------------------------------------ recording
@@ -365,17 +353,8 @@ def test_no_id_is_handed_to_two_draws(adev, runner, name, make, paired, entries)
 
 @pytest.fixture
 def host_dev():
-    from conftest import host_kernel_library
-    mods = (mcmc_host, hmc_host, flow_host)
-    host_backend.install(host_kernel_library())
-    for m in mods:
-        m.install()
-    try:
-        yield torch.device("cpu")
-    finally:
-        for m in mods:
-            m.uninstall()
-        host_backend.uninstall()
+    with host_routing.host(*ROUTERS) as dev:
+        yield dev
 
 
 def test_the_check_notices_an_id_handed_out_twice(host_dev, monkeypatch):
