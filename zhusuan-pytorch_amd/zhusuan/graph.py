@@ -40,15 +40,38 @@ Capture rules that this class takes care of (each one cost a crash while bench.p
     launched once on the DEFAULT stream were enough for ``capture_end`` to crash (a segmentation fault, ROCm 7.2 / torch 2.10,
     found in round 6 with bench.py's one-tuning-run-per-job pass): use a side stream there too;
   * ``capture_error_mode='thread_local'``, so that unrelated threads (e.g. a data loader) may keep calling HIP;
+  * Python's cyclic garbage collector runs once before a capture and not during it (``_capture``): a collection inside the
+    capture that frees a dead cycle holding HIP resources aborted the process;
   * nothing inside the step may copy from the host (``torch.as_tensor(python_scalar, device=...)`` does);
   * the warm-up steps are real optimizer steps; with ``restore=True`` parameters, optimizer state and the RNG state are
     put back afterwards, so that constructing a GraphedStep has no side effect on training.
 """
+import contextlib
+import gc
+
 import torch
 
 from . import _rng
 
 __all__ = ['GraphedStep', 'GraphedStages']
+
+
+@contextlib.contextmanager
+def _capture(graph, **kwargs):
+    """``torch.cuda.graph(graph, capture_error_mode='thread_local', **kwargs)`` with Python's cyclic collector out of the way.
+    torch no longer collects before a capture (``torch.compiler.config.force_cudagraph_gc`` is off by default), and a
+    generational collection that fires INSIDE the capture may free a dead cycle that holds HIP resources -- an earlier
+    GraphedStep with its hipGraph and private pool is one: its closures refer to it -- which aborts the process.  So: collect
+    first, and keep the collector off until the capture has ended."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, capture_error_mode="thread_local", **kwargs):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def _optimizer_state_tensors(optimizer):
@@ -132,19 +155,19 @@ class GraphedStep(object):
             def record():
                 if self._exchange is None:
                     g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    with _capture(g):
                         for _ in range(self.steps_per_replay):
                             self._static_loss = eager_step()
                     self.graphs = [g]
                 else:
                     ga = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(ga, capture_error_mode="thread_local"):
+                    with _capture(ga):
                         self._static_loss = self._compute()
                     self.graphs = [ga]
                     if self._opt_step is not None:
                         torch.cuda.synchronize()
                         gb = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
+                        with _capture(gb, pool=ga.pool()):
                             self._opt_step()
                         self.graphs.append(gb)
             if agree is None:
@@ -292,7 +315,7 @@ class GraphedStages(object):
                     continue
                 g = torch.cuda.CUDAGraph()
                 if agree is None:
-                    with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
+                    with _capture(g, pool=pool):
                         out = fn()
                 else:
                     # Several ranks record the same step: a capture that fails on ONE rank must not let the others run on into
@@ -301,7 +324,7 @@ class GraphedStages(object):
                     # all give the graphs up and run the SAME stages eagerly (same collectives, same sizes, same order).
                     ok, out = True, None
                     try:
-                        with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
+                        with _capture(g, pool=pool):
                             out = fn()
                     except Exception as e:            # noqa: BLE001
                         ok, self.capture_error = False, repr(e)
