@@ -1,4 +1,4 @@
-// The kernels' per-element arithmetic (csrc/zs_common.h, csrc/zs_iw_math.h: __host__ __device__) compiled for the HOST
+// The kernels' per-element arithmetic (csrc/zs_common.h, csrc/zs_elem_math.h, csrc/zs_iw_math.h: __host__ __device__) compiled for the HOST
 // and run under AddressSanitizer + UndefinedBehaviorSanitizer (tests/test_sanitizers.py):
 //     hipcc -x hip --cuda-host-only -fno-gpu-sanitize -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all ...
 // Every function is checked against a double-precision restatement of the reference formula it implements, over edge
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../zhusuan-pytorch_amd/csrc/zs_common.h"
+#include "../../zhusuan-pytorch_amd/csrc/zs_elem_math.h"
 #include "../../zhusuan-pytorch_amd/csrc/zs_iw_math.h"
 #include "../../zhusuan-pytorch_amd/csrc/zs_locscale_math.h"
 
@@ -75,10 +76,13 @@ static void test_normal_bernoulli_terms() {
   const float dif[] = {0.0f, 1e-8f, -0.3f, 2.5f, -40.0f};
   for (float s : sig)
     for (float d : dif) {
-      const float l2 = zs::log2_fast(s);
-      const float got = zs::normal_lp_term(d, l2 * ZS_LN2, zs::exp2_fast(-2.0f * l2));
+      float logstd, prec;
+      zs::normal_parts(s, logstd, prec);
+      const float got = zs::normal_term(d, logstd, prec);
       const double ls = log((double)s), want = -0.91893853320467274178 - ls - 0.5 * exp(-2.0 * ls) * (double)d * d;   // normal.py:121-124
-      expect(close_rel(got, want, 3e-6, 3e-6) || !isfinite(want), "normal_lp_term", got, want);
+      expect(close_rel(got, want, 3e-6, 3e-6) || !isfinite(want), "normal_parts + normal_term (float)", got, want);
+      expect(zs::normal_lp(d + 0.25f, 0.25f, s) == zs::normal_term((d + 0.25f) - 0.25f, logstd, prec), "normal_lp = parts + term (float)",
+             zs::normal_lp(d + 0.25f, 0.25f, s), got);
     }
   const float ps[] = {0.0f, 1e-9f, 1e-4f, 0.25f, 0.5f, 0.75f, 1.0f - 1e-7f, 1.0f};
   const float xs[] = {0.0f, 1.0f, 0.25f};
@@ -88,12 +92,14 @@ static void test_normal_bernoulli_terms() {
       const double want = (double)x * log((double)a) + (1.0 - (double)x) * log((double)b);
       const float got = zs::bern_lp2_term(p, x) * ZS_LN2;
       expect(close_rel(got, want, 3e-6, 3e-6), "bern_lp2_term", got, want);
+      expect(zs::bern_term(p, x) == got, "bern_term (float) = bern_lp2_term * ln 2", zs::bern_term(p, x), got);
       const double dwant = (double)x / (double)a - (1.0 - (double)x) / (double)b;
       const float dgot = zs::bern_dp(p, x);
       expect(close_rel(dgot, dwant, 3e-6, 1e-6), "bern_dp", dgot, dwant);
     }
   for (float l = -30.0f; l <= 30.0f; l += 0.37f)
-    expect(close_rel(zs::sigmoid_fast(l), 1.0 / (1.0 + exp(-(double)l)), 3e-6, 1e-30), "sigmoid_fast", zs::sigmoid_fast(l), 0);
+    expect(close_rel(zs::sigmoid_any(l), 1.0 / (1.0 + exp(-(double)l)), 3e-6, 1e-30) && zs::sigmoid_any(l) == zs::sigmoid_fast(l),
+           "sigmoid_any (float) = sigmoid_fast", zs::sigmoid_any(l), 0);
   int64_t q, r;
   const int64_t as[] = {0, 1, 12799, (1ll << 31) - 1, 1ll << 31, (1ll << 40) + 12345}, bs[] = {1, 7, 256, 83886, (1ll << 31) + 3};
   for (int64_t a : as)
@@ -101,6 +107,118 @@ static void test_normal_bernoulli_terms() {
       zs::divmod(a, b, q, r);
       expect(q == a / b && r == a % b && zs::mod_fast(a, b) == a % b, "divmod / mod_fast", (double)q, (double)(a / b));
     }
+}
+
+// ---- zs_elem_math.h: the two-rounding sample and the double overloads
+// a failing case prints its operands as well
+static void expect_ops(bool ok, const char* what, long double got, long double want, double a, double b, double c, double d) {
+  ++n_checks;
+  if (!ok) {
+    if (n_fail < 20)
+      fprintf(stderr, "FAIL %s: operands (%.17g, %.17g, %.17g, %.17g) got %.20Lg want %.20Lg\n", what, a, b, c, d, got, want);
+    ++n_fail;
+  }
+}
+static float fma_t(float a, float b, float c) { return fmaf(a, b, c); }
+static double fma_t(double a, double b, double c) { return fma(a, b, c); }
+// a value in [1, 2) with every mantissa bit drawn
+static void draw_1_2(uint32_t hi, uint32_t lo, float& v) { v = 1.0f + (float)(hi >> 9) * 1.1920928955078125e-07f; (void)lo; }
+static void draw_1_2(uint32_t hi, uint32_t lo, double& v) { v = 1.0 + (double)((((uint64_t)hi << 32) | lo) >> 12) * 2.220446049250313e-16; }
+
+// z = m + s * e must be the ROUNDED product plus m (normal.py:105, logistic.py:66, uniform.py:70), never fma(s, e, m)
+template <typename T>
+static void test_mul_add_2round(const char* what, T one_plus, T want_2round, T want_fused) {
+  // hand-derived: s = e = 1 + h, m = -1.  float, h = 2^-12: s * e = 1 + 2^-11 + 2^-24 is a tie and rounds to the even 1 + 2^-11,
+  // so the result is 2^-11 and the fused one 2^-11 + 2^-24.  double, h = 2^-27: s * e = 1 + 2^-26 + 2^-54 rounds down (a quarter
+  // of an ulp) to 1 + 2^-26: 2^-26 against the fused 2^-26 + 2^-54.
+  const T got = zs::mul_add_2round((T)-1, one_plus, one_plus);
+  expect_ops(got == want_2round && fma_t(one_plus, one_plus, (T)-1) == want_fused && got != want_fused, what, got, want_2round, -1, one_plus,
+             one_plus, want_fused);
+  long differ = 0;
+  for (uint64_t g = 0; g < 4000; ++g) {
+    const zs::Philox4 r = zs::philox4x32_10(g, 11, 0x5EEDull), q = zs::philox4x32_10(g, 12, 0x5EEDull);
+    T s, e, m;
+    draw_1_2(r.x, r.y, s);
+    draw_1_2(r.z, r.w, e);
+    draw_1_2(q.x, q.y, m);
+    // two kinds of m: the product nearly cancels (every low bit of the product shows), and an unrelated magnitude
+    const T ms[2] = {(T)-s, (T)((m - (T)1.5) * (T)(q.z & 1 ? 1e-3 : 1e3))};
+    for (T mm : ms) {
+      volatile T prod = s * e;                       // rounded to T here, whatever the compiler would like to contract
+      const T want = mm + prod, fused = fma_t(s, e, mm), z = zs::mul_add_2round(mm, s, e);
+      expect_ops(memcmp(&z, &want, sizeof(T)) == 0, what, z, want, mm, s, e, fused);
+      if (fused != want) {
+        ++differ;
+        expect_ops(z != fused, what, z, want, mm, s, e, fused);
+      }
+    }
+  }
+  expect_ops(differ > 1000, "mul_add_2round: the drawn triples tell the two roundings from one", differ, 1000, 0, 0, 0, 0);
+}
+
+// The double overloads against long double restatements over the operand grids of the float checks.  Bounds: U = 2^-52 is one
+// unit in the last place (relative); every libm call and every rounding of the expression contributes at most one unit of the
+// largest intermediate, so a bound is (number of libm calls + roundings) * U * (largest intermediate) -- plus, where a logarithm
+// feeds exp(-2 * .), that logarithm's one unit amplified: exp(-2 (L + U |L|)) = exp(-2 L) (1 - 2 |L| U), i.e. 2 |L| more units.
+static void test_double_overloads() {
+  const long double U = 2.220446049250313e-16L, C = -0.91893853320467274178032973640562L, E = (long double)ZS_BERN_EPS_D;
+  const float sig[] = {1e-6f, 1e-3f, 0.5f, 1.0f, 3.0f, 1e3f, 1e6f};
+  const float dif[] = {0.0f, 1e-8f, -0.3f, 2.5f, -40.0f};
+  for (float sf : sig)
+    for (float df : dif) {
+      const double s = sf, d = df;
+      double logstd, prec;
+      zs::normal_parts(s, logstd, prec);
+      const long double L = logl((long double)s), P = expl(-2.0L * L);
+      // logstd: one libm call.  prec: one libm call + the amplified unit of logstd (the product -2 * logstd is exact)
+      expect_ops(fabsl(logstd - L) <= U * fabsl(L), "normal_parts (double): log sigma", logstd, L, s, 0, 0, 0);
+      expect_ops(fabsl(prec - P) <= (1 + 2 * fabsl(L)) * U * P, "normal_parts (double): sigma^-2", prec, P, s, 0, 0, 0);
+      // normal_term on the SAME double operands: four roundings (c - logstd, d * d, (0.5 prec) * (d d), the difference; 0.5 * prec is exact)
+      const long double quad = 0.5L * prec * ((long double)d * d), want = (C - logstd) - quad, got = zs::normal_term(d, logstd, prec);
+      const long double big = fmaxl(fmaxl(fabsl(C - logstd), quad), fabsl(want));
+      expect_ops(fabsl(got - want) <= 4 * U * big, "normal_term (double)", got, want, d, logstd, prec, 0);
+      // normal_partials from the operands: x = mu + d, sigma given as sigma or as log sigma
+      for (int ls = 0; ls < 2; ++ls) {
+        const double mu = 0.75, x = mu + d, g = -1.7, op = ls ? log(s) : s;
+        double gx, gm, gs;
+        zs::normal_partials(x, mu, op, g, ls != 0, gx, gm, gs);
+        const long double sg = ls ? expl((long double)op) : (long double)op, Ls = logl(sg), pr = 1.0L / (sg * sg), dd = (long double)x - mu;
+        const long double t = g * pr * dd, q = pr * dd * dd, wgs = ls ? g * (q - 1.0L) : g * (q - 1.0L) / sg;
+        // t: three libm calls (exp when ls, log, exp) + three roundings (x - mu, g * prec, * d) + the amplified unit of the logarithm
+        expect_ops(fabsl(gx + t) <= (6 + 2 * fabsl(Ls)) * U * fabsl(t) && gm == -gx, "normal_partials (double): d/dx, d/dmu", gx, -t, x, mu, op, g);
+        // the sigma gradient: three libm calls + six roundings (x - mu, prec * d, * d, - 1, g *, / sigma) + the amplified unit, in units of
+        // the largest intermediate max(q, 1) (the difference q - 1 may cancel), scaled like the result by |g| [/ sigma]
+        const long double unit = fabsl(g) * fmaxl(q, 1.0L) / (ls ? 1.0L : sg);
+        expect_ops(fabsl(gs - wgs) <= (9 + 2 * fabsl(Ls)) * U * unit, "normal_partials (double): d/dsigma", gs, wgs, x, mu, op, g);
+      }
+    }
+  const float ps[] = {0.0f, 1e-9f, 1e-4f, 0.25f, 0.5f, 0.75f, 1.0f - 1e-7f, 1.0f};
+  const float xs[] = {0.0f, 1.0f, 0.25f};
+  for (float pf : ps) {
+    const double p = pf;
+    const long double a = (long double)p + E, b = (1.0L - p) + E, la = logl(a), lb = logl(b);
+    const long double lmax = fmaxl(fmaxl(fabsl(la), fabsl(lb)), 1.0L);       // (a rounding of a logarithm's ARGUMENT moves the logarithm by U: the 1)
+    for (float xf : xs) {
+      const double x = xf;
+      // nine: p + e, log, x *, 1 - x, 1 - p, + e, log, *, +
+      const long double want = x * la + (1.0L - x) * lb, got = zs::bern_term(p, x);
+      expect_ops(fabsl(got - want) <= 9 * U * lmax, "bern_term (double)", got, want, p, x, 0, 0);
+      // seven: p + e, /, 1 - x, 1 - p, + e, /, -
+      const long double da = x / a, db = (1.0L - x) / b, dwant = da - db, dgot = zs::bern_dp(p, x);
+      expect_ops(fabsl(dgot - dwant) <= 7 * U * fmaxl(fabsl(da), fabsl(db)), "bern_dp (double)", dgot, dwant, p, x, 0, 0);
+    }
+    // six: p + e, log, 1 - p, + e, log, -
+    const long double rgot = zs::log_ratio_any(p);
+    expect_ops(fabsl(rgot - (la - lb)) <= 6 * U * lmax, "log_ratio_any (double)", rgot, la - lb, p, 0, 0, 0);
+  }
+  for (float lf = -30.0f; lf <= 30.0f; lf += 0.37f) {
+    const double l = lf;
+    // three: exp, 1 +, 1 / -- each relative to the result (a relative U on exp(-l) is at most a relative U on 1 + exp(-l))
+    const long double want = 1.0L / (1.0L + expl(-(long double)l)), got = zs::sigmoid_any(l);
+    expect_ops(fabsl(got - want) <= 3 * U * want, "sigmoid_any (double)", got, want, l, 0, 0, 0);
+  }
+  expect_ops(zs::sigma_of(0.5, false) == 0.5 && zs::sigma_of(0.5, true) == exp(0.5) && zs::sigma_of(0.5f, true) == expf(0.5f),
+             "sigma_of", zs::sigma_of(0.5, true), exp(0.5), 0.5, 0, 0, 0);
 }
 
 // Logistic / Uniform element math of the shared kernels (zs_locscale_math.h) against float64 restatements of
@@ -299,6 +417,9 @@ int main() {
   test_philox_kat();
   test_uniform_and_normal();
   test_normal_bernoulli_terms();
+  test_mul_add_2round<float>("mul_add_2round (float)", 1.0f + 0x1p-12f, 0x1p-11f, 0x1p-11f + 0x1p-24f);
+  test_mul_add_2round<double>("mul_add_2round (double)", 1.0 + 0x1p-27, 0x1p-26, 0x1p-26 + 0x1p-54);
+  test_double_overloads();
   test_iw_particle();
   test_logistic_uniform_terms();
   if (n_fail) {

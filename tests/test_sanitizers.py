@@ -1,5 +1,6 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (GPU sanitizers are not available on this pool):
-(1) the kernels' own per-element arithmetic -- csrc/zs_common.h and csrc/zs_iw_math.h are __host__ __device__ -- compiled for
+(1) the kernels' own per-element arithmetic -- csrc/zs_common.h, csrc/zs_elem_math.h (Normal / Bernoulli terms in float and
+double, the two-rounding sample) and csrc/zs_iw_math.h are __host__ __device__ -- compiled for
 the host and checked against double-precision restatements (tests/host_math/zs_host_math.hip); (2) the C oracle.  The oracle's own tests -- golden fixtures, ragged / empty / unaligned shapes, every entry point of the C ABI,
 fp32 and fp64 -- are re-run in a child process against ``oracle/_build/libzs_oracle_asan.so``; any out-of-bounds access,
 use of uninitialised stack, signed overflow or misaligned access aborts that process."""

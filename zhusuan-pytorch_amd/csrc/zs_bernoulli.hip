@@ -293,7 +293,7 @@ __global__ __launch_bounds__(256) void k_bern_logprob_serial(
 // ------------------------------------------------------------------------------------
 
 // d/dp of the row term, x ra - (1 - x) rb, with its one fused multiply-add spelled out.  Left to the compiler (bern_dp,
-// zs_common.h) the two instantiations of k_bern_logprob_bwd_rows contracted different products -- the non-temporal one
+// zs_elem_math.h) the two instantiations of k_bern_logprob_bwd_rows contracted different products -- the non-temporal one
 // fma(-(1 - x), rb, x ra), the plain one fma(x, ra, -((1 - x) rb)) -- so a gradient changed in its last bits when the tensor
 // outgrew the Infinity Cache (tests/test_size_gated_variants.py, bb-K50-R33555-D40).  This is the plain instantiation's form.
 __device__ __forceinline__ float bern_dp_rows(float p, float x) {
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(256) void k_bern_logprob_bwd_longrow2d(
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     if (ok[u]) {
-      const float4 o = bern_piece_grad<LOGITS>(pv[u], xv[u], g);          // packed fp32 (zs_common.h)
+      const float4 o = bern_piece_grad<LOGITS>(pv[u], xv[u], g);          // packed fp32 (zs_elem_math.h)
       if (NT) {
         const zs_f4v v = {o.x, o.y, o.z, o.w};
         __builtin_nontemporal_store(v, reinterpret_cast<zs_f4v*>(&grow[lane + 64 * u]));
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(256) void k_iw1_bwd(
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     if (ok[u]) {
-      const float4 o = bern_piece_grad<LOGITS>(pv[u], xv[u], g);          // packed fp32 (zs_common.h)
+      const float4 o = bern_piece_grad<LOGITS>(pv[u], xv[u], g);          // packed fp32 (zs_elem_math.h)
       if (NT) {
         const zs_f4v v = {o.x, o.y, o.z, o.w};
         __builtin_nontemporal_store(v, reinterpret_cast<zs_f4v*>(&grow[lane + 64 * u]));
@@ -520,7 +520,7 @@ __global__ __launch_bounds__(256) void k_bern_logprob_bwd_xreuse(
       float4* __restrict__ grow = gp + row * D4;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const float4 o = bern_piece_grad<LOGITS>(pv[u], xv[u], g);        // packed fp32 (zs_common.h)
+        const float4 o = bern_piece_grad<LOGITS>(pv[u], xv[u], g);        // packed fp32 (zs_elem_math.h)
         if (ok[u]) {
           if (NT) {
             const zs_f4v vv = {o.x, o.y, o.z, o.w};

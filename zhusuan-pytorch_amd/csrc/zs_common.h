@@ -10,7 +10,6 @@
 #define ZS_WAVE 64
 #define ZS_LN2 0.69314718055994530942f
 #define ZS_NEG_HALF_LOG_2PI (-0.91893853320467274178f)  // -0.5*log(2*pi), normal.py:122
-#define ZS_BERN_EPS 1e-8f                                 // bernoulli.py:94
 
 #define ZS_CHECK_LAUNCH()                           \
   do {                                              \
@@ -148,97 +147,12 @@ ZS_HD float cos_rev(float x) {
 ZS_HD float ln_fast(float x) { return log2_fast(x) * ZS_LN2; }
 ZS_HD float exp_fast(float x) { return exp2_fast(x * 1.44269504088896340736f); }
 
-// Normal log-density term for one element given log2(sigma) and prec = sigma^-2
-// (normal.py:121-124: c - logstd - 0.5 * precision * (x - mean)^2).
-ZS_HD float normal_lp_term(float diff, float logstd, float prec) {
-  return (ZS_NEG_HALF_LOG_2PI - logstd) - 0.5f * prec * (diff * diff);
-}
-
-// Bernoulli term in log2 units (bernoulli.py:94); caller multiplies the row sum by ln 2.
-ZS_HD float bern_lp2_term(float p, float x) {
-  float a = log2_fast(p + ZS_BERN_EPS);
-  float b = log2_fast((1.0f - p) + ZS_BERN_EPS);
-  return x * a + (1.0f - x) * b;
-}
-// The same term for one 16-byte piece (four elements) in PACKED fp32 arithmetic (v_pk_add / v_pk_mul / v_pk_fma_f32: two elements
-// per instruction), accumulated pairwise into `acc`: per element 2.5 full-rate instructions + the two logarithms instead of 7 + 2.
-// The kernels that give a workgroup a fixed share of the rows (IW1) are bound by exactly this arithmetic.  `omx` = 1 - x.
+// packed fp32 pairs / quads (v_pk_*_f32 arithmetic, dwordx4 operands of inline assembly)
 typedef float zs_f2v __attribute__((ext_vector_type(2)));
 typedef float zs_f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void bern_piece_acc(const float4& p, const float4& x, const float4& omx, zs_f2v& acc) {
-  const zs_f2v eps = {ZS_BERN_EPS, ZS_BERN_EPS}, one = {1.0f, 1.0f};
-  const zs_f2v p0 = {p.x, p.y}, p1 = {p.z, p.w};
-  const zs_f2v a0 = p0 + eps, a1 = p1 + eps;
-  const zs_f2v b0 = (one - p0) + eps, b1 = (one - p1) + eps;
-  const zs_f2v la0 = {log2_fast(a0.x), log2_fast(a0.y)}, la1 = {log2_fast(a1.x), log2_fast(a1.y)};
-  const zs_f2v lb0 = {log2_fast(b0.x), log2_fast(b0.y)}, lb1 = {log2_fast(b1.x), log2_fast(b1.y)};
-  const zs_f2v x0 = {x.x, x.y}, x1 = {x.z, x.w}, o0 = {omx.x, omx.y}, o1 = {omx.z, omx.w};
-  acc += __builtin_elementwise_fma(o0, lb0, x0 * la0);
-  acc += __builtin_elementwise_fma(o1, lb1, x1 * la1);
-}
-// The same piece when every x of the row is exactly 0 or 1 (binarised observations: the examples' data): with s = 2x - 1 and
-// c = 1 - x the selected argument is fma(p, s, c) -- p for x = 1, 1 - p (rounded as above) for x = 0 -- and the term is ONE
-// logarithm: x * la + (1 - x) * lb has a factor exactly 1 and a factor exactly 0.  Bit-identical to bern_piece_acc for every p
-// whose two arguments are positive (any p in [0, 1]); for an invalid p (outside [-1e-8, 1 + 1e-8]) the general form returns NaN
-// through 0 * log(negative) where this one does not evaluate the other branch.
-__device__ __forceinline__ void bern_piece_acc_bits(const float4& p, const float4& s, zs_f2v& acc) {
-  const zs_f2v eps = {ZS_BERN_EPS, ZS_BERN_EPS}, half = {0.5f, 0.5f}, mhalf = {-0.5f, -0.5f};
-  const zs_f2v p0 = {p.x, p.y}, p1 = {p.z, p.w}, s0 = {s.x, s.y}, s1 = {s.z, s.w};
-  const zs_f2v c0 = __builtin_elementwise_fma(s0, mhalf, half), c1 = __builtin_elementwise_fma(s1, mhalf, half);     // 1 - x, exactly
-  const zs_f2v a0 = __builtin_elementwise_fma(p0, s0, c0) + eps, a1 = __builtin_elementwise_fma(p1, s1, c1) + eps;
-  const zs_f2v l0 = {log2_fast(a0.x), log2_fast(a0.y)}, l1 = {log2_fast(a1.x), log2_fast(a1.y)};
-  acc += l0;
-  acc += l1;
-}
-// ... with s = 2x - 1 AND c = 1 - x handed in (both parked in LDS once per datapoint by the persistent fused kernel): the same bits
-// for rows of 0s and 1s, two packed instructions fewer per piece.  (s = 0, c = 1 makes the piece contribute log 1 = 0: padding.)
-__device__ __forceinline__ void bern_piece_acc_bits2(const float4& p, const float4& s, const float4& c, zs_f2v& acc) {
-  const zs_f2v eps = {ZS_BERN_EPS, ZS_BERN_EPS};
-  const zs_f2v p0 = {p.x, p.y}, p1 = {p.z, p.w}, s0 = {s.x, s.y}, s1 = {s.z, s.w}, c0 = {c.x, c.y}, c1 = {c.z, c.w};
-  const zs_f2v a0 = __builtin_elementwise_fma(p0, s0, c0) + eps, a1 = __builtin_elementwise_fma(p1, s1, c1) + eps;
-  const zs_f2v l0 = {log2_fast(a0.x), log2_fast(a0.y)}, l1 = {log2_fast(a1.x), log2_fast(a1.y)};
-  acc += l0;
-  acc += l1;
-}
-// Gradient of that term w.r.t. p for one 16-byte piece, times the row gradient g, in packed fp32 arithmetic:
-//   g * (x / (p + eps) - (1 - x) / ((1 - p) + eps))            [LOGITS: p = sigmoid(l), result times p (1 - p)]
-// 3.5 packed instructions + two reciprocals per element instead of ~9 + 2: K3's backward stalls on instruction issue for half
-// of its wave cycles (SQ_WAIT_INST_ANY 0.50 at 6.6 GB, 0.59 in IW1's merged backward; profiles/r04_pmc_*.json).
-template <bool LOGITS>
-__device__ __forceinline__ float4 bern_piece_grad(const float4& pl, const float4& x, float g) {
-  const zs_f2v eps = {ZS_BERN_EPS, ZS_BERN_EPS}, one = {1.0f, 1.0f}, gg = {g, g};
-  zs_f2v p0 = {pl.x, pl.y}, p1 = {pl.z, pl.w};
-  if (LOGITS) {
-    p0.x = rcp_fast(1.0f + exp_fast(-p0.x)); p0.y = rcp_fast(1.0f + exp_fast(-p0.y));
-    p1.x = rcp_fast(1.0f + exp_fast(-p1.x)); p1.y = rcp_fast(1.0f + exp_fast(-p1.y));
-  }
-  const zs_f2v q0 = one - p0, q1 = one - p1;
-  const zs_f2v a0 = p0 + eps, a1 = p1 + eps, b0 = q0 + eps, b1 = q1 + eps;
-  const zs_f2v ra0 = {rcp_fast(a0.x), rcp_fast(a0.y)}, ra1 = {rcp_fast(a1.x), rcp_fast(a1.y)};
-  const zs_f2v rb0 = {rcp_fast(b0.x), rcp_fast(b0.y)}, rb1 = {rcp_fast(b1.x), rcp_fast(b1.y)};
-  const zs_f2v x0 = {x.x, x.y}, x1 = {x.z, x.w};
-  zs_f2v t0 = __builtin_elementwise_fma(x0 - one, rb0, x0 * ra0);          // x ra - (1 - x) rb
-  zs_f2v t1 = __builtin_elementwise_fma(x1 - one, rb1, x1 * ra1);
-  t0 = gg * t0;
-  t1 = gg * t1;
-  if (LOGITS) {
-    t0 = t0 * p0 * q0;
-    t1 = t1 * p1 * q1;
-  }
-  return make_float4(t0.x, t0.y, t1.x, t1.y);
-}
-// torch.sigmoid: 1 / (1 + exp(-l)), bernoulli.py:50
-ZS_HD float sigmoid_fast(float l) { return rcp_fast(1.0f + exp_fast(-l)); }
-// d/dp of x*log(p+e) + (1-x)*log((1-p)+e)
-ZS_HD float bern_dp(float p, float x) {
-  return x * rcp_fast(p + ZS_BERN_EPS) - (1.0f - x) * rcp_fast((1.0f - p) + ZS_BERN_EPS);
-}
-
-// d/dx of x*log(p+e) + (1-x)*log((1-p)+e) = log(p+e) - log((1-p)+e): the gradient w.r.t. the observation (bernoulli.py:94)
-ZS_HD float log_ratio_any(float p) { return (log2_fast(p + ZS_BERN_EPS) - log2_fast((1.0f - p) + ZS_BERN_EPS)) * ZS_LN2; }
-ZS_HD double log_ratio_any(double p) { return log(p + 1e-8) - log((1.0 - p) + 1e-8); }
-ZS_HD float sigmoid_any(float l) { return sigmoid_fast(l); }
-ZS_HD double sigmoid_any(double l) { return 1.0 / (1.0 + exp(-l)); }
+// (The per-element arithmetic of the Normal and Bernoulli families, float and double, is zs_elem_math.h.)
+ZS_HD float max_of(float a, float b) { return fmaxf(a, b); }
+ZS_HD double max_of(double a, double b) { return fmax(a, b); }
 
 // ---------------------------------------------------------------- index arithmetic
 // 64-bit integer division expands to ~100 VALU instructions on CDNA; row / tile indices almost always fit
@@ -266,10 +180,54 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, ZS_WAVE));
   return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, ZS_WAVE));
+  return v;
+}
+// Reductions over a 256-thread workgroup through four LDS slots (`sh`: four T), valid in every thread.  The sum comes in the
+// TWO orders its callers were written with -- they differ in the last bits, and every call site keeps its own: the one-launch
+// kernels and R1 add the four wave totals pairwise, the IW reductions (zs_iw.hip, zs_f64.hip) one after the other.
+template <typename T>
+__device__ __forceinline__ void block_park_256(T v, T* sh) {       // lane 0 of each wave parks its wave's value
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+}
+template <typename T>
+__device__ __forceinline__ T block_sum_256(T v, T* sh) {           // (sh[0] + sh[1]) + (sh[2] + sh[3])
+  block_park_256(wave_sum(v), sh);
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+template <typename T>
+__device__ __forceinline__ T block_sum_256_seq(T v, T* sh) {       // sh[0] + sh[1] + sh[2] + sh[3]
+  block_park_256(wave_sum(v), sh);
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+template <typename T>
+__device__ __forceinline__ T block_max_256(T v, T* sh) {
+  block_park_256(wave_max(v), sh);
+  return max_of(max_of(sh[0], sh[1]), max_of(sh[2], sh[3]));
+}
+__device__ __forceinline__ int block_min_256(int v, int* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int t = __shfl_xor(v, o, ZS_WAVE);
+    v = t < v ? t : v;
+  }
+  block_park_256(v, sh);
+  const int a = sh[0] < sh[1] ? sh[0] : sh[1], c = sh[2] < sh[3] ? sh[2] : sh[3];
+  return a < c ? a : c;
 }
 // The same reductions by DPP (row-of-16 butterflies, then the row totals passed up by row_bcast:15 / :31): 6 VALU instructions
 // with the result in LANE 63 -- the __shfl_xor butterflies above are 6 ds_bpermute round trips through the LDS crossbar, a

@@ -3,32 +3,13 @@
 // BASELINE.json's configs uses them, so these are straightforward one-thread-per-row / one-workgroup-per-
 // datapoint kernels with libm-grade double math: correct and coalesced where D = 1, not tuned.
 // Draws: the same Philox4x32-10 + Box-Muller stream as the fp32 kernels (24-bit uniforms), widened to double.
-#include "zs_common.h"
+#include "zs_elem_math.h"
 #include "../../include/zs_hip.h"
 
 using namespace zs;
 
 namespace {
 
-constexpr double kC = -0.91893853320467274178;  // -0.5*log(2*pi)
-constexpr double kEps = 1e-8;                   // bernoulli.py:94
-
-__device__ __forceinline__ double normal_term(double x, double mu, double sigma) {
-  const double logstd = log(sigma);             // normal.py:121
-  const double precision = exp(-2.0 * logstd);  // normal.py:123
-  const double d = x - mu;
-  return (kC - logstd) - 0.5 * precision * (d * d);
-}
-__device__ __forceinline__ double bern_term(double p, double x) {
-  return x * log(p + kEps) + (1.0 - x) * log((1.0 - p) + kEps);
-}
-__device__ __forceinline__ double sig_of(double v, bool ls) { return ls ? exp(v) : v; }   // Normal(logstd=...), normal.py:56
-__device__ __forceinline__ double sigmoid_d(double l) { return 1.0 / (1.0 + exp(-l)); }
-__device__ __forceinline__ double mul_add_2round(double m, double s, double e) {
-#pragma clang fp contract(off)   // two roundings like the reference's separate mul and add (normal.py:105)
-  const double prod = s * e;
-  return m + prod;
-}
 __device__ __forceinline__ double eps_at(const double* eps, int64_t i, uint64_t seed, uint64_t call) {
   if (eps) return eps[i];
   return (double)f4_get(philox_normal4((uint64_t)(i >> 2), call, seed), (int)(i & 3));
@@ -48,10 +29,10 @@ __global__ __launch_bounds__(256) void k64_normal_sample(const double* __restric
     double acc = 0.0;
     for (int64_t d = 0; d < D; ++d) {
       const int64_t m = r * D + d, i = k * M + m;
-      const double sg = sig_of(sigma[m], ls);
+      const double sg = sigma_of(sigma[m], ls);
       const double zz = mul_add_2round(mu[m], sg, eps_at(eps, i, seed, call));
       z[i] = zz;
-      if (lp) acc += normal_term(zz, mu[m], sg);
+      if (lp) acc += normal_lp(zz, mu[m], sg);
     }
     if (lp) lp[k * sk + r * sr] = acc;
   }
@@ -75,7 +56,7 @@ __global__ __launch_bounds__(256) void k64_normal_sample_bwd(const double* __res
       if (glp) g += glp[k * gsk + r * gsr];
     }
     gmu[m] = a;
-    const double sg = sig_of(sigma[m], ls);
+    const double sg = sigma_of(sigma[m], ls);
     gsigma[m] = ls ? b * sg - g : b - g / sg;
   }
 }
@@ -89,23 +70,12 @@ __global__ __launch_bounds__(256) void k64_normal_logprob(const double* __restri
     double acc = 0.0;
     for (int64_t d = 0; d < D; ++d) {
       const int64_t i = row * D + d;
-      acc += normal_term(x[mod_fast(i, Px)], mu[mod_fast(i, Pm)], sig_of(sigma[mod_fast(i, Ps)], ls));
+      acc += normal_lp(x[mod_fast(i, Px)], mu[mod_fast(i, Pm)], sigma_of(sigma[mod_fast(i, Ps)], ls));
     }
     int64_t k, r;
     divmod(row, R, k, r);
     lp[k * sk + r * sr] = acc;
   }
-}
-
-__device__ __forceinline__ void normal_partials(double x, double mu, double sigma, double g, double& gx, double& gm, double& gs,
-                                                bool ls) {
-  sigma = sig_of(sigma, ls);
-  const double prec = exp(-2.0 * log(sigma));
-  const double d = x - mu;
-  const double t = g * prec * d;
-  gx = -t;
-  gm = t;
-  gs = ls ? g * (prec * d * d - 1.0) : g * (prec * d * d - 1.0) / sigma;   // d/d logstd = sigma * d/d sigma
 }
 
 __global__ __launch_bounds__(256) void k64_normal_logprob_bwd(const double* __restrict__ x, int64_t Px, const double* __restrict__ mu,
@@ -118,7 +88,7 @@ __global__ __launch_bounds__(256) void k64_normal_logprob_bwd(const double* __re
     divmod(i, D, row, dd);
     divmod(row, R, k, r);
     double a, b, c;
-    normal_partials(x[mod_fast(i, Px)], mu[mod_fast(i, Pm)], sigma[mod_fast(i, Ps)], glp[k * gsk + r * gsr], a, b, c, ls);
+    normal_partials(x[mod_fast(i, Px)], mu[mod_fast(i, Pm)], sigma[mod_fast(i, Ps)], glp[k * gsk + r * gsr], ls, a, b, c);
     if (gx) gx[i] = a;
     if (gmu) gmu[i] = b;
     if (gsigma) gsigma[i] = c;
@@ -137,7 +107,7 @@ __global__ __launch_bounds__(256) void k64_normal_logprob_bwd_ksum(const double*
     double sa = 0.0, sb = 0.0;
     for (int64_t k = 0; k < K; ++k) {
       double a, b, c;
-      normal_partials(x[k * M + m], mu[m], sigma[m], gscale ? glp[k * gsk + r * gsr] * gs : glp[k * gsk + r * gsr], a, b, c, ls);
+      normal_partials(x[k * M + m], mu[m], sigma[m], gscale ? glp[k * gsk + r * gsr] * gs : glp[k * gsk + r * gsr], ls, a, b, c);
       if (gx) gx[k * M + m] = a;
       sa += b;
       sb += c;
@@ -158,7 +128,7 @@ __global__ __launch_bounds__(256) void k64_bern_logprob(const double* __restrict
       const int64_t i = row * D + d;
       double pv = p[i];
       if (LOGITS) {
-        pv = sigmoid_d(pv);
+        pv = sigmoid_any(pv);
         if (probs_out) probs_out[i] = pv;
       }
       acc += bern_term(pv, x[mod_fast(i, Px)]);
@@ -180,13 +150,13 @@ __global__ __launch_bounds__(256) void k64_bern_logprob_bwd(const double* __rest
     divmod(row, R, k, r);
     double pv = p[i], scale = 1.0;
     if (LOGITS) {
-      pv = sigmoid_d(pv);
+      pv = sigmoid_any(pv);
       scale = pv * (1.0 - pv);
     }
     const double xv = x[mod_fast(i, Px)];
     double g = glp[k * gsk + r * gsr];
     if (gscale) g *= gscale[r * gss];
-    gp[i] = g * (xv / (pv + kEps) - (1.0 - xv) / ((1.0 - pv) + kEps)) * scale;
+    gp[i] = g * bern_dp(pv, xv) * scale;
   }
 }
 
@@ -207,44 +177,7 @@ __global__ __launch_bounds__(256) void k64_philox_normal(double* __restrict__ ou
     out[i] = eps_at(nullptr, i, seed, call);
 }
 
-// ---- importance-weighted reduction, one 256-thread workgroup per datapoint (any K)
-__device__ __forceinline__ double wsum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);
-  return v;
-}
-__device__ __forceinline__ double wmax_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, ZS_WAVE));
-  return v;
-}
-__device__ __forceinline__ double bsum_d(double v, double* sh) {
-  v = wsum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-__device__ __forceinline__ double bmax_d(double v, double* sh) {
-  v = wmax_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-}
-__device__ __forceinline__ int bmin_i(int v, int* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int t = __shfl_xor(v, o, ZS_WAVE);
-    v = t < v ? t : v;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const int a = sh[0] < sh[1] ? sh[0] : sh[1], c = sh[2] < sh[3] ? sh[2] : sh[3];
-  return a < c ? a : c;
-}
-
+// ---- importance-weighted reduction, one 256-thread workgroup per datapoint (any K); sums in zs_iw.hip's order (block_sum_256_seq)
 struct IwExt64 {   // extras of zs_iw_objective_f64 (zs_iw.hip: IwExt)
   const double* logp_b;
   int64_t ld_b;
@@ -278,7 +211,7 @@ __global__ __launch_bounds__(256) void k64_iw_reduce(const double* __restrict__ 
       mx = fmax(mx, l);
       sl += l;
     }
-    const double m1 = bmax_d(mx, shf), sumL = bsum_d(sl, shf);
+    const double m1 = block_max_256(mx, shf), sumL = block_sum_256_seq(sl, shf);
     int jm = 0x7fffffff;
     double s = 0.0;
     for (int64_t k = threadIdx.x; k < K; k += 256) {
@@ -286,18 +219,18 @@ __global__ __launch_bounds__(256) void k64_iw_reduce(const double* __restrict__ 
       if (l == m1 && (int)k < jm) jm = (int)k;
       s += exp(l - m1);
     }
-    const int jstar = bmin_i(jm, shi);
-    const double S = bsum_d(s, shf);
+    const int jstar = block_min_256(jm, shi);
+    const double S = block_sum_256_seq(s, shf);
     double m2 = -INFINITY, S2 = 0.0;
     if (estimator == ZS_IW_VIMCO) {
       double t = -INFINITY;
       for (int64_t k = threadIdx.x; k < K; k += 256)
         if ((int)k != jstar) t = fmax(t, ZS_LW(k));
-      m2 = bmax_d(t, shf);
+      m2 = block_max_256(t, shf);
       double s2 = 0.0;
       for (int64_t k = threadIdx.x; k < K; k += 256)
         if ((int)k != jstar) s2 += exp(ZS_LW(k) - m2);
-      S2 = bsum_d(s2, shf);
+      S2 = block_sum_256_seq(s2, shf);
     }
     const double logS = log(S), invKm1 = K > 1 ? 1.0 / (double)(K - 1) : 0.0;
     double ct = 0.0;
@@ -317,7 +250,7 @@ __global__ __launch_bounds__(256) void k64_iw_reduce(const double* __restrict__ 
       if (coef_p) coef_p[b * K + k] = -wt * ext.scale;
       if (coef_q) coef_q[b * K + k] = cq * ext.scale;
     }
-    const double cost = bsum_d(ct, shf);
+    const double cost = block_sum_256_seq(ct, shf);
     my_cost += cost;
     if (threadIdx.x == 0) {
       if (cost_b) cost_b[b] = cost;
@@ -338,7 +271,7 @@ __global__ __launch_bounds__(256) void k64_iw_reduce(const double* __restrict__ 
       double s = 0.0;
       for (unsigned i = threadIdx.x; i < gridDim.x; i += 64)
         s += __hip_atomic_load(ext.partials + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s = wsum_d(s);
+      s = wave_sum(s);
       if (threadIdx.x == 0) {
         ext.mean_cost[0] = s * ext.inv_B;
         *ext.ticket = 0u;
@@ -354,10 +287,10 @@ __global__ __launch_bounds__(256) void k64_lme(const double* __restrict__ x, int
     const double* __restrict__ xx = x + b * ld;
     double mx = -INFINITY;
     for (int64_t k = threadIdx.x; k < K; k += 256) mx = fmax(mx, xx[k]);
-    const double m = bmax_d(mx, shf);
+    const double m = block_max_256(mx, shf);
     double s = 0.0;
     for (int64_t k = threadIdx.x; k < K; k += 256) s += exp(xx[k] - m);
-    const double S = bsum_d(s, shf);
+    const double S = block_sum_256_seq(s, shf);
     if (threadIdx.x == 0) out[b] = log(S / (double)K) + m;
   }
 }
@@ -544,7 +477,7 @@ __global__ __launch_bounds__(256) void k64_mean_of(const double* __restrict__ v,
   __shared__ double sh[4];
   double s = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += 256) s += v[i];
-  s = bsum_d(s, sh);
+  s = block_sum_256_seq(s, sh);
   if (threadIdx.x == 0) out[0] = s / (double)n;
 }
 

@@ -231,34 +231,7 @@ __global__ __launch_bounds__(256) void k_iw_reduce_group(
   }
 }
 
-// ---- any K: one 256-thread workgroup per datapoint, LDS-staged partials
-__device__ __forceinline__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-__device__ __forceinline__ float block_max(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__device__ __forceinline__ int block_min_int(int v, int* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    int t = __shfl_xor(v, o, ZS_WAVE);
-    v = t < v ? t : v;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int a = sh[0] < sh[1] ? sh[0] : sh[1], c = sh[2] < sh[3] ? sh[2] : sh[3];
-  return a < c ? a : c;
-}
-
+// ---- any K: one 256-thread workgroup per datapoint, LDS-staged partials (zs_common.h; the four wave totals added in sequence)
 __global__ __launch_bounds__(256) void k_iw_reduce_block(
     const float* __restrict__ logp, int64_t ld_p, const float* __restrict__ logq, int64_t ld_q,
     int64_t B, int64_t K, int estimator, float* __restrict__ cost_b, float* __restrict__ bound_b,
@@ -279,8 +252,8 @@ __global__ __launch_bounds__(256) void k_iw_reduce_block(
       sl += l;
     }
     IwRow r;
-    r.m1 = block_max(mx, shf);
-    r.sumL = block_sum(sl, shf);
+    r.m1 = block_max_256(mx, shf);
+    r.sumL = block_sum_256_seq(sl, shf);
     // pass 2: first arg-max, S
     int jm = 0x7fffffff;
     float s = 0.f;
@@ -289,19 +262,19 @@ __global__ __launch_bounds__(256) void k_iw_reduce_block(
       if (l == r.m1 && (int)k < jm) jm = (int)k;
       s += expf(l - r.m1);
     }
-    r.jstar = block_min_int(jm, shi);
-    r.S = block_sum(s, shf);
+    r.jstar = block_min_256(jm, shi);
+    r.S = block_sum_256_seq(s, shf);
     r.m2 = -INFINITY;
     r.S2 = 0.f;
     if (estimator == ZS_IW_VIMCO) {
       float m2 = -INFINITY;
       for (int64_t k = threadIdx.x; k < K; k += 256)
         if ((int)k != r.jstar) m2 = fmaxf(m2, ZS_LW(k));
-      r.m2 = block_max(m2, shf);
+      r.m2 = block_max_256(m2, shf);
       float s2 = 0.f;
       for (int64_t k = threadIdx.x; k < K; k += 256)
         if ((int)k != r.jstar) s2 += expf(ZS_LW(k) - r.m2);
-      r.S2 = block_sum(s2, shf);
+      r.S2 = block_sum_256_seq(s2, shf);
     }
     r.logS = logf(r.S);
     r.invK = 1.0f / (float)K;
@@ -316,7 +289,7 @@ __global__ __launch_bounds__(256) void k_iw_reduce_block(
       if (coef_p) coef_p[b * K + k] = -wt * ext.scale;
       if (coef_q) coef_q[b * K + k] = cq * ext.scale;
     }
-    const float cost = block_sum(ct, shf);
+    const float cost = block_sum_256_seq(ct, shf);
     my_cost += cost;
     if (threadIdx.x == 0) {
       if (cost_b) cost_b[b] = cost;
@@ -421,10 +394,10 @@ __global__ __launch_bounds__(256) void k_lme_block(const float* __restrict__ x, 
     const float* __restrict__ xx = x + b * ld;
     float mx = -INFINITY;
     for (int64_t k = threadIdx.x; k < K; k += 256) mx = fmaxf(mx, xx[k]);
-    const float m = block_max(mx, shf);
+    const float m = block_max_256(mx, shf);
     float s = 0.f;
     for (int64_t k = threadIdx.x; k < K; k += 256) s += exp_fast(xx[k] - m);
-    const float S = block_sum(s, shf);
+    const float S = block_sum_256_seq(s, shf);
     if (threadIdx.x == 0) out[b] = ln_fast(S / (float)K) + m;
   }
 }

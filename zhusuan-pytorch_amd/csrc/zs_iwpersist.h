@@ -28,7 +28,7 @@
 //     tail wave WATCHES the shard words until both counts are complete and stores the mean (iw1_watch, below).  +inf / -inf / NaN costs raise sticky flags of their own: the
 //     mean is then +inf / -inf / NaN as the fp32 mean the reference takes (importance_weighted_objective.py:191) would be.
 #pragma once
-#include "zs_common.h"
+#include "zs_elem_math.h"
 #include "zs_iw_math.h"
 #include "zs_iw1_args.h"
 #include "../../include/zs_hip.h"

@@ -52,6 +52,9 @@ __device__ __forceinline__ void pl_stage_gpre(T* __restrict__ dst, const T* __re
 }
 template <typename T>
 __host__ __device__ __forceinline__ bool pl_al(const void* p) { return (((uintptr_t)p) & (4 * sizeof(T) - 1)) == 0; }
+// sqrt(n) in T: the layer's 1/sqrt(n_in + 1) scale (sqrtf for float, sqrt for double)
+template <typename T>
+__device__ __forceinline__ T sqrt_n(int64_t n) { return sqrt((T)n); }
 
 // the last arrival's reduction: gk[e] = (sum over the tiles t, in tile order, of p0[t * tile_stride + e]) / p for e < nW.
 // Four consecutive weight elements per thread and load when everything is 16-byte aligned, 16 tiles in flight: ntiles = 64
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(256) void k_particle_linear(const T* __restrict__ h
     ws[o * WS + i] = wk[e];
   }
   __syncthreads();
-  const T p = Mth<T>::sqrt_n(n_in + 1);                           // torch.sqrt(torch.as_tensor(h.shape[2])), bnn_vi.py:42
+  const T p = sqrt_n<T>(n_in + 1);                           // torch.sqrt(torch.as_tensor(h.shape[2])), bnn_vi.py:42
   T* __restrict__ ok = out + ((int64_t)k * B + b0) * n_out;
   for (int e = threadIdx.x; e < nb * n_out; e += 256) {
     const int b = e / n_out, o = e - b * n_out;
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(256) void k_particle_linear_bwd(const T* __restrict
                                                              int ntiles, int bt) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   __shared__ bool last;
-  const T p = Mth<T>::sqrt_n(n_in + 1);
+  const T p = sqrt_n<T>(n_in + 1);
   const int WS = n_in + 1, nW = n_out * (n_in + 1);
   T* gs = reinterpret_cast<T*>(smem_raw);                     // [bt][n_out] flat
   T* hs = gs + ((bt * n_out + 3) & ~3);                        // [bt][n_in] flat
@@ -304,7 +307,7 @@ __global__ __launch_bounds__(256) void k_particle_mlp(const PMArgs<T> A, const T
     if (l >= A.L) break;
     const int n_in = A.n[l], n_out = A.n[l + 1], WS = pl_odd(n_in + 1);
     const bool relu = l < A.L - 1;
-    const T p = Mth<T>::sqrt_n(n_in + 1);
+    const T p = sqrt_n<T>(n_in + 1);
     const T* __restrict__ wl = wsm + A.woff[l];
     T* __restrict__ ok = A.out[l] + ((int64_t)k * B + b0) * n_out;
     for (int e = threadIdx.x; e < nb * n_out; e += 256) {
@@ -366,7 +369,7 @@ __global__ __launch_bounds__(256) void k_particle_mlp_bwd(const PMArgs<T> A, con
     const int l = L - 1 - ll;
     if (l < 0) break;
     const int n_in = A.n[l], n_out = A.n[l + 1], nW = n_out * (n_in + 1), WS = n_in + 1;
-    const T p = Mth<T>::sqrt_n(n_in + 1);
+    const T p = sqrt_n<T>(n_in + 1);
     const T* __restrict__ in = sm + A.ioff[l];
     T* __restrict__ pk = slab + A.poff[l];
     for (int e = threadIdx.x; e < nW; e += 256) {   // the tile's partial weight gradient (unscaled: / p in the reduction)
@@ -414,7 +417,7 @@ __global__ __launch_bounds__(256) void k_particle_mlp_bwd(const PMArgs<T> A, con
     for (int l = 0; l < PM_MAX_LAYERS; ++l) {
       if (l >= L) break;
       const int nW = A.n[l + 1] * (A.n[l] + 1);
-      pl_reduce_tiles<T>(p0 + A.poff[l], A.slab, A.gw[l] + (int64_t)k * nW, nW, ntiles, Mth<T>::sqrt_n(A.n[l] + 1));
+      pl_reduce_tiles<T>(p0 + A.poff[l], A.slab, A.gw[l] + (int64_t)k * nW, nW, ntiles, sqrt_n<T>(A.n[l] + 1));
     }
     if (threadIdx.x == 0) ticket_return(tickets + k);
   }
@@ -819,7 +822,7 @@ __global__ __launch_bounds__(PR_BLOCK) void k_particle_rmse(const T* __restrict_
     const T d = y[b] - ((s0 + s1) + (s2 + s3)) / Kf;         // torch.mean: the sum divided by K
     acc += (double)d * (double)d;
   }
-  acc = wave_sum_d(acc);
+  acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
   __syncthreads();
   double tot = 0.0;
@@ -840,7 +843,7 @@ __global__ __launch_bounds__(PR_BLOCK) void k_particle_rmse(const T* __restrict_
   if (!last) return;
   double s = 0.0;
   for (unsigned i = threadIdx.x; i < gridDim.x; i += PR_BLOCK) s += load_wt(ws + i);    // (<= PR_MAX_BLOCKS: one load per thread)
-  s = wave_sum_d(s);
+  s = wave_sum(s);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
   __syncthreads();

@@ -34,15 +34,6 @@ __device__ __forceinline__ float t_log1p(float e) { return log2_fast(1.0f + e) *
 __device__ __forceinline__ double t_log1p(double e) { return log1p(e); }
 __device__ __forceinline__ float t_abs(float x) { return fabsf(x); }
 __device__ __forceinline__ double t_abs(double x) { return fabs(x); }
-__device__ __forceinline__ float t_max(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ double t_max(double a, double b) { return fmax(a, b); }
-
-template <typename T>
-__device__ __forceinline__ T mul_add_2round(T a, T b, T e) {
-#pragma clang fp contract(off)   // loc + scale * eps rounds twice like the reference (logistic.py:66, uniform.py:70)
-  const T prod = b * e;
-  return a + prod;
-}
 
 // Logistic log-density of x (logistic.py:81-82): -t - 2*softplus(-t) - log(scale), t = (x - loc)/scale,
 // softplus(-t) = max(-t, 0) + log1p(exp(-|t|)).
@@ -50,7 +41,7 @@ template <typename T>
 __device__ __forceinline__ T logistic_term(T x, T loc, T scale) {
   const T t = (x - loc) / scale;
   const T e = t_exp(-t_abs(t));
-  const T sp = t_max(-t, (T)0) + t_log1p(e);
+  const T sp = max_of(-t, (T)0) + t_log1p(e);
   return (-t - (T)2 * sp) - t_log(scale);
 }
 
@@ -465,7 +456,7 @@ __global__ __launch_bounds__(256) void k_long_rows(F f, T* __restrict__ lp, int6
         if (j < cnt) acc += t[j];
     }
     if (want) {
-      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, ZS_WAVE);
+      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, ZS_WAVE);   // (= wave_sum; written out: the call is scheduled differently)
       __syncthreads();
       if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
       __syncthreads();

@@ -67,34 +67,18 @@ struct Fam {
   static constexpr bool bern_logits = FAM == ZS_LJ_BERNOULLI_LOGITS || FAM == LJ_BERNOULLI_LOGITS_GX;
   static constexpr bool has_gx = has_b || bern_gx;          // families whose first operand can receive a gradient
   static __device__ __forceinline__ T term(T x, T a, T b) {
-    typedef Mth<T> M;
     if (FAM == ZS_LJ_ROWS) return x;
-    if (has_b) {
-      const T sg = M::sigma_of(b, FAM == ZS_LJ_NORMAL_LOGSTD);
-      T logstd, prec;
-      M::parts(sg, logstd, prec);
-      return M::normal_term(x - a, logstd, prec);
-    }
-    return M::bern_term(bern_logits ? M::sigmoid(a) : a, x);
+    if (has_b) return normal_lp(x, a, sigma_of(b, FAM == ZS_LJ_NORMAL_LOGSTD));
+    return bern_term(bern_logits ? sigmoid_any(a) : a, x);
   }
   // d term / d (x, a, b) times gc = g * coef
   static __device__ __forceinline__ void partials(T x, T a, T b, T gc, T& dx, T& da, T& db) {
-    typedef Mth<T> M;
     if (has_b) {
-      const bool ls = FAM == ZS_LJ_NORMAL_LOGSTD;
-      const T sg = M::sigma_of(b, ls);
-      T logstd, prec;
-      M::parts(sg, logstd, prec);
-      const T d = x - a;
-      const T u = gc * prec * d;
-      dx = -u;
-      da = u;
-      const T v = gc * (prec * d * d - (T)1);
-      db = ls ? v : v / sg;                     // d/d log std = sigma * d/d sigma
+      normal_partials(x, a, b, gc, FAM == ZS_LJ_NORMAL_LOGSTD, dx, da, db);
     } else {                                    // Bernoulli: d/d probs, or d/d logits = d/dp * p * (1 - p)
       db = (T)0;
-      const T p = bern_logits ? M::sigmoid(a) : a;
-      da = gc * M::bern_dp(p, x) * (bern_logits ? p * ((T)1 - p) : (T)1);
+      const T p = bern_logits ? sigmoid_any(a) : a;
+      da = gc * bern_dp(p, x) * (bern_logits ? p * ((T)1 - p) : (T)1);
       dx = bern_gx ? gc * log_ratio_any(p) : (T)0;          // d/dx = log(p + 1e-8) - log(1 - p + 1e-8)
     }
   }
@@ -394,7 +378,7 @@ __global__ __launch_bounds__(LJ_BLOCK) void k_logjoint_bwd(const LJArgs<T> A, co
         if (!dst || cls != CLS_SCALAR) continue;
         double s = 0.0;
         for (unsigned i = threadIdx.x; i < t.nblocks; i += 64) s += load_wt(ws + 3 * (t.block0 + i) + o);
-        s = wave_sum_d(s);
+        s = wave_sum(s);
         if (threadIdx.x == 0) dst[0] = (T)s;
       }
     }
@@ -566,19 +550,6 @@ struct MSArgs {
   int64_t total_waves;
 };
 
-template <typename T>
-__device__ __forceinline__ T ms_mul_add_2round(T m, T s, T e) {
-#pragma clang fp contract(off)   // z = mean + std * eps rounds twice like the reference's separate mul and add (normal.py:105)
-  const T prod = s * e;
-  return m + prod;
-}
-template <typename T>
-__device__ __forceinline__ T wave_sum_t(T v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);
-  return v;
-}
-
 // forward: `wpr` wavefronts per (term, particle, row); lanes take the Philox groups (4 consecutive flat elements) that touch
 // the row -- for the shapes this kernel is for (rows of up to ~1000 elements) every lane has at most one group: ONE round
 // of parameter loads, the draw, one round of stores.  A workgroup's four wavefronts belong to one term (its Philox call id
@@ -586,7 +557,6 @@ __device__ __forceinline__ T wave_sum_t(T v) {
 template <typename T>
 __global__ __launch_bounds__(256) void k_normal_sample_multi(const MSArgs<T> A, uint64_t seed, const uint64_t* __restrict__ rs,
                                                              uint64_t* __restrict__ rng_used) {
-  typedef Mth<T> Mh;
   __shared__ T part[4];
   uint64_t base = 0;
   if (rs) { seed = rs[0]; base = rs[1]; }
@@ -627,15 +597,15 @@ __global__ __launch_bounds__(256) void k_normal_sample_multi(const MSArgs<T> A, 
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const T s = Mh::sigma_of(sg[j], ls);
-        const T zz = ms_mul_add_2round<T>(mu[j], s, e[j]);
+        const T s = sigma_of(sg[j], ls);
+        const T zz = mul_add_2round(mu[j], s, e[j]);
         if (in[j]) t.z[i0 + j] = zz;
         T logstd, prec;
-        Mh::parts(s, logstd, prec);
-        if (in[j]) acc += Mh::normal_term(zz - mu[j], logstd, prec);
+        normal_parts(s, logstd, prec);
+        if (in[j]) acc += normal_term(zz - mu[j], logstd, prec);
       }
     }
-    acc = wave_sum_t<T>(acc);
+    acc = wave_sum(acc);
   }
   if (lane == 0) part[wv] = acc;
   __syncthreads();
@@ -650,7 +620,6 @@ __global__ __launch_bounds__(256) void k_normal_sample_multi(const MSArgs<T> A, 
 // (One thread per element walking all K particles was K dependent rounds of loads + K Philox regenerations in sequence.)
 template <typename T>
 __global__ __launch_bounds__(256) void k_normal_sample_multi_bwd(const MSArgs<T> A, uint64_t seed, const uint64_t* __restrict__ rs) {
-  typedef Mth<T> Mh;
   __shared__ T red[3][256];
   uint64_t base = 0;
   if (rs) { seed = rs[0]; base = rs[1]; }
@@ -689,7 +658,7 @@ __global__ __launch_bounds__(256) void k_normal_sample_multi_bwd(const MSArgs<T>
       g += red[2][j * MP + mp];
     }
     t.gmu[m] = a;
-    const T sg = Mh::sigma_of(t.sigma[m], t.ls != 0);
+    const T sg = sigma_of(t.sigma[m], t.ls != 0);
     t.gsigma[m] = t.ls ? b * sg - g : b - g / sg;
   }
 }

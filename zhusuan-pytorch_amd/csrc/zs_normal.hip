@@ -161,8 +161,8 @@ __global__ __launch_bounds__(256) void k_normal_sample_longrow(
         const float dv[4] = {zz.x - m.x, zz.y - m.y, zz.z - m.z, zz.w - m.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          float l2 = log2_fast(sv[j]);
-          acc += normal_lp_term(dv[j], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
+          const float l2 = log2_fast(sv[j]);
+          acc += normal_term(dv[j], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
         }
       }
     }
@@ -211,10 +211,7 @@ __global__ __launch_bounds__(256) void k_normal_sample_serial(
       const float mm = mu[m], s = sigma_of(sigma[m], ls);
       const float zz = mul_add_2round(mm, s, e);
       z[i] = zz;
-      if (lp) {
-        float l2 = log2_fast(s);
-        acc += normal_lp_term(zz - mm, l2 * ZS_LN2, exp2_fast(-2.0f * l2));
-      }
+      if (lp) acc += normal_lp(zz, mm, s);
     }
     if (lp) lp[k * sk + r * sr] = acc;
   }
@@ -245,10 +242,7 @@ __global__ __launch_bounds__(256) void k_normal_sample_waverow(
       const float mm = mu[m], s = sigma_of(sigma[m], ls);
       const float zz = mul_add_2round(mm, s, e);
       z[i] = zz;
-      if (lp) {
-        const float l2 = log2_fast(s);
-        acc += normal_lp_term(zz - mm, l2 * ZS_LN2, exp2_fast(-2.0f * l2));
-      }
+      if (lp) acc += normal_lp(zz, mm, s);
     }
     if (lp) {
       acc = wave_sum(acc);
@@ -270,9 +264,7 @@ __global__ __launch_bounds__(256) void k_normal_logprob_waverow(
     for (int64_t d = lane; d < D; d += 64) {
       const int64_t i = row * D + d;
       const float s = sigma_of(sigma[Ps == 1 ? 0 : mod_fast(i, Ps)], ls);
-      const float l2 = log2_fast(s);
-      acc += normal_lp_term(x[Px == 1 ? 0 : mod_fast(i, Px)] - mu[Pm == 1 ? 0 : mod_fast(i, Pm)], l2 * ZS_LN2,
-                            exp2_fast(-2.0f * l2));
+      acc += normal_lp(x[Px == 1 ? 0 : mod_fast(i, Px)], mu[Pm == 1 ? 0 : mod_fast(i, Pm)], s);
     }
     acc = wave_sum(acc);
     if (lane == 0) {
@@ -437,8 +429,8 @@ __global__ __launch_bounds__(256) void k_normal_logprob_rows(
         const float dv[4] = {xv.x - m.x, xv.y - m.y, xv.z - m.z, xv.w - m.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          float l2 = log2_fast(sv[j]);
-          acc += normal_lp_term(dv[j], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
+          const float l2 = log2_fast(sv[j]);
+          acc += normal_term(dv[j], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
         }
       }
     }
@@ -485,10 +477,10 @@ __global__ __launch_bounds__(256) void k_normal_logprob_blockrow(
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (SS) {
-          acc += normal_lp_term(dv[j], l2s * ZS_LN2, ps);
+          acc += normal_term(dv[j], l2s * ZS_LN2, ps);
         } else {
           const float l2 = log2_fast(sv[j]);
-          acc += normal_lp_term(dv[j], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
+          acc += normal_term(dv[j], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
         }
       }
     }
@@ -542,7 +534,7 @@ __global__ __launch_bounds__(256) void k_normal_logprob_full(
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const float l2 = log2_fast(sv[j]);
-            acc += normal_lp_term(dv[j], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
+            acc += normal_term(dv[j], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
           }
         }
       }
@@ -568,8 +560,8 @@ __global__ __launch_bounds__(256) void k_normal_logprob_serial(
     for (int64_t d = 0; d < D; ++d) {
       const int64_t i = row * D + d;
       const float s = sigma_of(sigma[mod_fast(i, Ps)], ls);
-      const float l2 = log2_fast(s);
-      acc += normal_lp_term(x[mod_fast(i, Px)] - mu[mod_fast(i, Pm)], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
+      const float l2 = log2_fast(s);                 // (spelled out: through normal_lp this loop is scheduled differently)
+      acc += normal_term(x[mod_fast(i, Px)] - mu[mod_fast(i, Pm)], l2 * ZS_LN2, exp2_fast(-2.0f * l2));
     }
     int64_t k, r;
     divmod(row, R, k, r);

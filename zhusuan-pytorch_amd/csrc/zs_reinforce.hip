@@ -88,6 +88,8 @@ constexpr int R1_ONE_BLOCK_MAX = 16384;
 constexpr int R1_BLOCK = 256;
 constexpr unsigned R1_MAX_BLOCKS = 2048;
 
+// zs_common.h's block_sum_256 with its butterfly written out, like block_sum_1024 above: called through wave_sum(double) the same
+// sums come out with the LDS address formed one instruction earlier, and this file's machine code is kept as it was.
 __device__ __forceinline__ double block_sum_r1(double v, double* sh) {       // 256 threads; valid in every thread
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, ZS_WAVE);

@@ -3,30 +3,13 @@
 #pragma once
 #include <stdlib.h>
 
-#include "zs_common.h"
+#include "zs_elem_math.h"
 #include "zs_locscale_math.h"
 
 namespace zs {
 
 enum { D_NORMAL = 0, D_LOGISTIC = 1, D_UNIFORM = 2 };
 
-// round-to-nearest mul / add that the compiler may not contract into an FMA: the sample
-// z = mean + std * eps must round twice like the reference's separate mul and add
-// (normal.py:105) so that z is bit-identical for identical eps.
-__device__ __forceinline__ float mul_add_2round(float m, float s, float e) {
-#pragma clang fp contract(off)   // HIP's __fmul_rn/__fadd_rn are plain * and + and would still fuse
-  const float prod = s * e;
-  return m + prod;
-}
-
-// `sigma` operand given as log(sigma) (Normal(logstd=...), normal.py:56: std = exp(logstd)): the kernels form sigma
-// themselves instead of the caller launching an exp (and a multiply in backward).  Precise expf: it runs once per
-// parameter, not per particle.  d/d logstd = sigma * d/d sigma.
-__device__ __forceinline__ float sigma_of(float v, bool is_logstd) { return is_logstd ? expf(v) : v; }
-__device__ __forceinline__ float4 sigma_of(float4 v, bool is_logstd) {
-  if (is_logstd) { v.x = expf(v.x); v.y = expf(v.y); v.z = expf(v.z); v.w = expf(v.w); }
-  return v;
-}
 // resolved Philox ids of a draw, written once per launch for the backward call (which may run after the caller has
 // advanced the live rng_state)
 __device__ __forceinline__ void publish_rng(uint64_t* __restrict__ rng_used, uint64_t seed, uint64_t call) {
