@@ -9,7 +9,8 @@ kernels of include/zs_flow.h.
 
 Categorical / OnehotCategorical and their relaxations ExpConcrete / Concrete (upstream ZhuSuan has them, the PyTorch reference
 dropped them) run on the categorical kernels of include/zs_cat.h, a library of its own that is loaded on their first use;
-MultivariateNormalCholesky (the same history) runs on the triangular kernels of include/zs_mvn.h, likewise."""
+MultivariateNormalCholesky (the same history) runs on the triangular kernels of include/zs_mvn.h, likewise.  AdmixtureMultinomial
+(the likelihood of the reference's unfinished logistic-normal topic model) runs on the matrix-core kernels of include/zs_topic.h."""
 from .base import Distribution
 from .normal import Normal
 from .bernoulli import Bernoulli
@@ -19,6 +20,7 @@ from .torch_families import Beta, Exponential, Gamma, Laplace, Poisson, StudentT
 from .categorical import Categorical, OnehotCategorical, Discrete, OnehotDiscrete
 from .concrete import ExpConcrete, Concrete, ExpGumbelSoftmax, GumbelSoftmax
 from .multivariate import MultivariateNormalCholesky
+from .admixture import AdmixtureMultinomial
 
 __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # torch.distributions pass-throughs (no kernels) and the flow-defined distribution:
@@ -27,4 +29,6 @@ __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            'Categorical', 'OnehotCategorical', 'Discrete', 'OnehotDiscrete', 'ExpConcrete', 'Concrete', 'ExpGumbelSoftmax',
            'GumbelSoftmax',
            # the triangular kernels (include/zs_mvn.h):
-           'MultivariateNormalCholesky']
+           'MultivariateNormalCholesky',
+           # the admixture likelihood (include/zs_topic.h):
+           'AdmixtureMultinomial']

@@ -5,7 +5,8 @@ import torch.nn as nn
 
 from .stochastic_tensor import StochasticTensor, node_value
 from ..distributions import (Distribution, Normal, Bernoulli, Logistic, Uniform, Beta, Exponential, Gamma, Laplace, Poisson,
-                             StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete, MultivariateNormalCholesky)
+                             StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete, MultivariateNormalCholesky,
+                             AdmixtureMultinomial)
 
 __all__ = ['BayesianNet']
 
@@ -29,6 +30,8 @@ name_mapping = {
     "Concrete": Concrete,
     # the triangular kernels (include/zs_mvn.h)
     "MultivariateNormalCholesky": MultivariateNormalCholesky,
+    # the admixture likelihood (include/zs_topic.h)
+    "AdmixtureMultinomial": AdmixtureMultinomial,
 }
 
 
@@ -222,3 +225,11 @@ class BayesianNet(nn.Module):
         return self._family_node(MultivariateNormalCholesky, name, n_samples,
                                  dict(mean=mean, cov_tril=cov_tril, dtype=dtype, is_reparameterized=is_reparameterized,
                                       group_ndims=group_ndims), kwargs)
+
+    # include/zs_topic.h: the likelihood of the logistic-normal topic model; the node must be observed (no sampler)
+    def admixture_multinomial(self, name, doc_logits, topic_logits, dtype=None, group_ndims=0, n_samples=None, **kwargs):
+        if isinstance(name, str) and name not in self.observed:
+            from ..distributions.admixture import NO_SAMPLE
+            raise NotImplementedError(NO_SAMPLE % (" node '%s'" % name))
+        return self._family_node(AdmixtureMultinomial, name, n_samples,
+                                 dict(doc_logits=doc_logits, topic_logits=topic_logits, dtype=dtype, group_ndims=group_ndims), kwargs)
