@@ -10,7 +10,8 @@ kernels of include/zs_flow.h.
 Categorical / OnehotCategorical and their relaxations ExpConcrete / Concrete (upstream ZhuSuan has them, the PyTorch reference
 dropped them) run on the categorical kernels of include/zs_cat.h, a library of its own that is loaded on their first use;
 MultivariateNormalCholesky (the same history) runs on the triangular kernels of include/zs_mvn.h, likewise.  AdmixtureMultinomial
-(the likelihood of the reference's unfinished logistic-normal topic model) runs on the matrix-core kernels of include/zs_topic.h."""
+(the likelihood of the reference's unfinished logistic-normal topic model) runs on the matrix-core kernels of include/zs_topic.h,
+MatrixVariateNormalCholesky (upstream has it, the reference dropped it) on those of include/zs_matvar.h."""
 from .base import Distribution
 from .normal import Normal
 from .bernoulli import Bernoulli
@@ -21,6 +22,7 @@ from .categorical import Categorical, OnehotCategorical, Discrete, OnehotDiscret
 from .concrete import ExpConcrete, Concrete, ExpGumbelSoftmax, GumbelSoftmax
 from .multivariate import MultivariateNormalCholesky
 from .admixture import AdmixtureMultinomial
+from .matrix_variate import MatrixVariateNormalCholesky
 
 __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # torch.distributions pass-throughs (no kernels) and the flow-defined distribution:
@@ -31,4 +33,6 @@ __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # the triangular kernels (include/zs_mvn.h):
            'MultivariateNormalCholesky',
            # the admixture likelihood (include/zs_topic.h):
-           'AdmixtureMultinomial']
+           'AdmixtureMultinomial',
+           # the matrix-variate normal (include/zs_matvar.h):
+           'MatrixVariateNormalCholesky']

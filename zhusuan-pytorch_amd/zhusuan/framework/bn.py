@@ -6,7 +6,7 @@ import torch.nn as nn
 from .stochastic_tensor import StochasticTensor, node_value
 from ..distributions import (Distribution, Normal, Bernoulli, Logistic, Uniform, Beta, Exponential, Gamma, Laplace, Poisson,
                              StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete, MultivariateNormalCholesky,
-                             AdmixtureMultinomial)
+                             AdmixtureMultinomial, MatrixVariateNormalCholesky)
 
 __all__ = ['BayesianNet']
 
@@ -32,6 +32,8 @@ name_mapping = {
     "MultivariateNormalCholesky": MultivariateNormalCholesky,
     # the admixture likelihood (include/zs_topic.h)
     "AdmixtureMultinomial": AdmixtureMultinomial,
+    # the matrix-variate normal (include/zs_matvar.h)
+    "MatrixVariateNormalCholesky": MatrixVariateNormalCholesky,
 }
 
 
@@ -233,3 +235,10 @@ class BayesianNet(nn.Module):
             raise NotImplementedError(NO_SAMPLE % (" node '%s'" % name))
         return self._family_node(AdmixtureMultinomial, name, n_samples,
                                  dict(doc_logits=doc_logits, topic_logits=topic_logits, dtype=dtype, group_ndims=group_ndims), kwargs)
+
+    # include/zs_matvar.h: a normal over n x p matrices with row covariance U U^T and column covariance V V^T
+    def matrix_variate_normal_cholesky(self, name, mean, u_tril, v_tril, dtype=None, is_reparameterized=True, group_ndims=0,
+                                       n_samples=None, **kwargs):
+        return self._family_node(MatrixVariateNormalCholesky, name, n_samples,
+                                 dict(mean=mean, u_tril=u_tril, v_tril=v_tril, dtype=dtype, is_reparameterized=is_reparameterized,
+                                      group_ndims=group_ndims), kwargs)
