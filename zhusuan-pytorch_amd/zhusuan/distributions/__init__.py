@@ -11,7 +11,8 @@ Categorical / OnehotCategorical and their relaxations ExpConcrete / Concrete (up
 dropped them) run on the categorical kernels of include/zs_cat.h, a library of its own that is loaded on their first use;
 MultivariateNormalCholesky (the same history) runs on the triangular kernels of include/zs_mvn.h, likewise.  AdmixtureMultinomial
 (the likelihood of the reference's unfinished logistic-normal topic model) runs on the matrix-core kernels of include/zs_topic.h,
-MatrixVariateNormalCholesky (upstream has it, the reference dropped it) on those of include/zs_matvar.h."""
+MatrixVariateNormalCholesky (upstream has it, the reference dropped it) on those of include/zs_matvar.h, NormalMixture (a
+mixture-of-Gaussians / VampPrior density) on those of include/zs_mix.h."""
 from .base import Distribution
 from .normal import Normal
 from .bernoulli import Bernoulli
@@ -23,6 +24,7 @@ from .concrete import ExpConcrete, Concrete, ExpGumbelSoftmax, GumbelSoftmax
 from .multivariate import MultivariateNormalCholesky
 from .admixture import AdmixtureMultinomial
 from .matrix_variate import MatrixVariateNormalCholesky
+from .mixture import NormalMixture
 
 __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # torch.distributions pass-throughs (no kernels) and the flow-defined distribution:
@@ -35,4 +37,6 @@ __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # the admixture likelihood (include/zs_topic.h):
            'AdmixtureMultinomial',
            # the matrix-variate normal (include/zs_matvar.h):
-           'MatrixVariateNormalCholesky']
+           'MatrixVariateNormalCholesky',
+           # the mixture of Gaussians (include/zs_mix.h):
+           'NormalMixture']

@@ -6,7 +6,7 @@ import torch.nn as nn
 from .stochastic_tensor import StochasticTensor, node_value
 from ..distributions import (Distribution, Normal, Bernoulli, Logistic, Uniform, Beta, Exponential, Gamma, Laplace, Poisson,
                              StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete, MultivariateNormalCholesky,
-                             AdmixtureMultinomial, MatrixVariateNormalCholesky)
+                             AdmixtureMultinomial, MatrixVariateNormalCholesky, NormalMixture)
 
 __all__ = ['BayesianNet']
 
@@ -241,4 +241,11 @@ class BayesianNet(nn.Module):
                                        n_samples=None, **kwargs):
         return self._family_node(MatrixVariateNormalCholesky, name, n_samples,
                                  dict(mean=mean, u_tril=u_tril, v_tril=v_tril, dtype=dtype, is_reparameterized=is_reparameterized,
+                                      group_ndims=group_ndims), kwargs)
+
+    # include/zs_mix.h: a mixture of C diagonal Gaussians over D-vectors (a learned prior: mixture of Gaussians, VampPrior)
+    def normal_mixture(self, name, logits, mean, std=None, logstd=None, batch_shape=(), dtype=None, group_ndims=0, n_samples=None,
+                       **kwargs):
+        return self._family_node(NormalMixture, name, n_samples,
+                                 dict(logits=logits, mean=mean, std=std, logstd=logstd, batch_shape=batch_shape, dtype=dtype,
                                       group_ndims=group_ndims), kwargs)
