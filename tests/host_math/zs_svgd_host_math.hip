@@ -31,7 +31,7 @@ static void check_pairs(int K) {
       ++seen.at(bi * nb + bj);
       for (int lane = 0; lane < 64; ++lane) {
         for (int v = 0; v < 4; ++v) {
-          const int r = 16 * bi + zs::SvgdTile<T>::acc_row(lane >> 4, v), c = 16 * bj + (lane & 15);
+          const int r = 16 * bi + zs::MfmaTile<T>::acc_row(lane >> 4, v), c = 16 * bj + (lane & 15);
           if (r < K && c < K) {
             ++written.at((size_t)r * K + c);
             if (bi != bj) ++written.at((size_t)c * K + r);

@@ -3,12 +3,12 @@
 //
 // A torch composition of the node is a chain of tril, expand, matmul, solve_triangular, diagonal, log and sum launches that
 // materialises [K, R, n, n] and [K, R, p, p] expansions of the factors and keeps them for the backward.  Here an event lives in
-// LDS as a tile of 16 x 16 blocks (zs_matvar_math.h: MatvarTile, the budget) and every product and every substitution step runs on
+// LDS as a tile of 16 x 16 blocks (zs_matvar_math.h: the padding, the budget) and every product and every substitution step runs on
 // v_mfma_{f32,f64}_16x16x4; the factors are read from memory block by block as operands (all particles of a row read the same
 // factor: it stays in L2), blocks above the diagonal are never read and never multiplied.
 //
 // A lane l = 16 q + m of a wave holds, for step s of a 16 x 16 block product, A[m][4 s + q] and B[4 s + q][m], and leaves with
-// D[acc_row(q, v)][m], v = 0..3.  Two things follow, and the whole file is built on them:
+// D[acc_row(q, v)][m], v = 0..3 (zs_tile_math.h).  Two things follow, and the whole file is built on them:
 //   * an accumulator can be the B operand of the next product as it stands, with the contraction index of step v taken as
 //     acc_row(q, v) and the A operand read at that index (the order of a sum's terms is free).  The substitution step
 //     Y_i = inv(L_ii) (D_i - sum_j L_ij Y_j) is two chained products with the difference formed in registers.
@@ -32,31 +32,6 @@ namespace {
 
 constexpr int THREADS = ZS_MATVAR_THREADS;
 
-typedef float matvar_f4 __attribute__((ext_vector_type(4)));
-typedef double matvar_d4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Mfma;
-template <> struct Mfma<float> {
-  typedef matvar_f4 Acc;
-  static __device__ __forceinline__ Acc run(float a, float b, Acc c) {
-#if ZS_ON_DEVICE
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#else
-    return c;
-#endif
-  }
-};
-template <> struct Mfma<double> {
-  typedef matvar_d4 Acc;
-  static __device__ __forceinline__ Acc run(double a, double b, Acc c) {
-#if ZS_ON_DEVICE
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-#else
-    return c;
-#endif
-  }
-};
-
 // what a kernel knows about its event and its place
 template <typename T>
 struct Geo {
@@ -67,12 +42,10 @@ struct Geo {
 
 template <typename T>
 __device__ __forceinline__ Geo<T> geo_of(int n, int p) {
-  extern __shared__ __align__(16) unsigned char matvar_lds_bytes[];
   Geo<T> g;
-  g.n = n, g.p = p, g.nbn = matvar_blocks(n), g.nbp = matvar_blocks(p), g.ld = matvar_ld(p);
-  const int lane = threadIdx.x & 63;
-  g.m = lane & 15, g.q = lane >> 4, g.wave = threadIdx.x >> 6;
-  g.s0 = reinterpret_cast<T*>(matvar_lds_bytes);
+  g.n = n, g.p = p, g.nbn = blocks16(n), g.nbp = blocks16(p), g.ld = matvar_ld(p);
+  g.m = mfma_m(threadIdx.x), g.q = mfma_q(threadIdx.x), g.wave = mfma_wave(threadIdx.x);
+  g.s0 = tile_lds<T>();
   g.s1 = g.s0 + 16 * g.nbn * g.ld;
   g.inv = g.s1 + 16 * g.nbn * g.ld;
   g.red = g.inv + 256 * (g.nbn + g.nbp);
@@ -204,13 +177,13 @@ __device__ __forceinline__ void solve(const Geo<T>& g, T* S, int sa, int sb, int
       Acc y = {0, 0, 0, 0};
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int k = MatvarTile<T>::acc_row(g.q, v);
+        const int k = MfmaTile<T>::acc_row(g.q, v);
         const T r = col[(16 * i + k) * sa] - acc[v];
         const T a = TRANS ? inv[256 * i + k * 16 + g.m] : inv[256 * i + g.m * 16 + k];
         y = Mfma<T>::run(a, r, y);
       }
 #pragma unroll
-      for (int v = 0; v < 4; ++v) col[(16 * i + MatvarTile<T>::acc_row(g.q, v)) * sa] = y[v];
+      for (int v = 0; v < 4; ++v) col[(16 * i + MfmaTile<T>::acc_row(g.q, v)) * sa] = y[v];
     }
     wave_lds_order();          // the next block row reads what OTHER LANES OF THIS WAVE wrote: no other wave's blocks
   }
@@ -242,7 +215,7 @@ __device__ __forceinline__ void left_multiply(const Geo<T>& g, T* S, const T* __
         }
       }
 #pragma unroll
-      for (int v = 0; v < 4; ++v) col[(16 * ib + MatvarTile<T>::acc_row(g.q, v)) * g.ld] = acc[v];
+      for (int v = 0; v < 4; ++v) col[(16 * ib + MfmaTile<T>::acc_row(g.q, v)) * g.ld] = acc[v];
     }
   }
   __syncthreads();
@@ -266,7 +239,7 @@ __device__ __forceinline__ void right_multiply(const Geo<T>& g, T* S, const T* _
       }
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int r = 16 * ib + MatvarTile<T>::acc_row(g.q, v), c = 16 * jb + g.m;
+        const int r = 16 * ib + MfmaTile<T>::acc_row(g.q, v), c = 16 * jb + g.m;
         if (DRAW) {
           if (r < g.n && c < g.p) out[r * g.p + c] = mean[r * g.p + c] + acc[v];
         } else {
@@ -301,7 +274,7 @@ __device__ __forceinline__ void gram_lower(const Geo<T>& g, const T* Sx, const T
       }
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int r = 16 * bi + MatvarTile<T>::acc_row(g.q, v), c = 16 * bj + g.m;
+        const int r = 16 * bi + MfmaTile<T>::acc_row(g.q, v), c = 16 * bj + g.m;
         if (r < dim && c < dim) {
           const T val = w * acc[v];
           part[r * dim + c] = first ? val : part[r * dim + c] + val;
@@ -490,7 +463,7 @@ __global__ __launch_bounds__(THREADS) void k_matvar_finish(const T* __restrict__
 template <typename T>
 int check_shape(bool pointers, int64_t K, int64_t R, int64_t n, int64_t p) {
   if (!pointers || n < 1 || p < 1 || K < 0 || R < 0) return ZS_EINVAL;
-  if (n > MatvarTile<T>::MAX_DIM || p > MatvarTile<T>::MAX_DIM) return ZS_ENOTSUP;
+  if (n > MatvarCap<T>::MAX_DIM || p > MatvarCap<T>::MAX_DIM) return ZS_ENOTSUP;
   const int64_t grid_max = ((int64_t)1 << 31) - 1;
   if (K > 0 && R > 0 && K > grid_max / R) return ZS_ENOTSUP;                                   // a workgroup per event
   if (R > grid_max / matvar_part_stride(n, p) * ZS_MATVAR_THREADS) return ZS_ENOTSUP;          // the finish: a thread per element of a row's gradients

@@ -1,52 +1,44 @@
-// The arithmetic of MatrixVariateNormalCholesky (include/zs_matvar.h) that is not scheduling: the geometry of the two matrix
-// instructions, the LDS budget and the caps that follow from it, the split of the particles into shares, the layout of the
+// The arithmetic of MatrixVariateNormalCholesky (include/zs_matvar.h) that is not scheduling: the padding of an event's tile,
+// the LDS budget and the caps that follow from it, the split of the particles into shares, the layout of the
 // partials workspace, and the per-element expressions.  __host__ __device__ like the other *_math.h headers; zs_matvar.hip only
 // stages, multiplies, substitutes and reduces.
 #pragma once
 #include "zs_common.h"
 #include "zs_flat_math.h"
 #include "zs_group_math.h"
+#include "zs_tile_math.h"
 
 #define ZS_MATVAR_THREADS 256          // four waves
 #define ZS_MATVAR_WAVES 4
 #define ZS_MATVAR_MAX_DIM_F32 128
 #define ZS_MATVAR_MAX_DIM_F64 64
-#define ZS_MATVAR_PAD 12               // LD = p16 + 12, see MatvarTile
+#define ZS_MATVAR_PAD 12               // LD = p16 + 12, see below
 #define ZS_MATVAR_GRID_TARGET 256      // backward: workgroups wanted when the rows alone are fewer (one per CU)
 #define ZS_MATVAR_MAX_SHARES 16        // backward: at most this many partials per row, whatever K is
 #define ZS_MATVAR_LDS_BYTES (160 * 1024)
 
 namespace zs {
 
-// v_mfma_*_16x16x4 (the geometry of zs_topic_math.h, restated: that header is held bit for bit by the topic tests and stays as it
-// is): lane l = 16 q + m holds A[i = m][k = q], B[k = q][j = m] and four values D[acc_row(q, v)][j = m].  The two element types
-// differ ONLY in acc_row: the f32 instruction gives a lane four consecutive rows, the f64 one every fourth row.
-//
-// An event is held in LDS as a tile of n16 x LD elements, n16 / p16 = n / p rounded up to 16, LD = p16 + 12.  LD = 4 (4 j + 3) is
-// four times an odd number: the 64 addresses m LD + 4 s + q of an operand read along a row (m = 0..15, q = 0..3) fall into 64
-// different float32 banks, and the four k-rows (4 s + q) LD + m of an operand read down a column start 12 banks apart.
+// An event is held in LDS as a tile of n16 x LD elements (the lanes' places in it: zs_tile_math.h), n16 / p16 = n / p rounded up
+// to 16, LD = p16 + 12.  LD = 4 (4 j + 3) is four times an odd number: the 64 addresses m LD + 4 s + q of an operand read along a
+// row (m = 0..15, q = 0..3) fall into 64 different float32 banks (float64: every bank twice, the least possible), and the four
+// k-rows (4 s + q) LD + m of an operand read down a column start in four different banks, LD mod 64 = 12, 28, 44 or 60 apart.
 //
 // LDS budget (bytes; two tiles, the staged inverses of the 16 x 16 diagonal blocks of both factors, four reduction slots):
 //   float32, n = p = 128:  2 * 128 * 140 * 4 = 143 360;  inverses (8 + 8) * 256 * 4 = 16 384;  slots 16;  total 159 760 <= 163 840
 //   float64, n = p =  64:  2 *  64 *  76 * 8 =  77 824;  inverses (4 + 4) * 256 * 8 = 16 384;  slots 32;  total  94 240
 //   float64, n = p = 128:  2 * 128 * 140 * 8 = 286 720: does not fit (nor does 96: 190 464); the float64 cap is half the float32
 //   one, 64, the element sizes' ratio.
-template <typename T> struct MatvarTile;
-template <> struct MatvarTile<float> {
-  static constexpr int MAX_DIM = ZS_MATVAR_MAX_DIM_F32;
-  static ZS_HD int acc_row(int q, int v) { return 4 * q + v; }
-};
-template <> struct MatvarTile<double> {
-  static constexpr int MAX_DIM = ZS_MATVAR_MAX_DIM_F64;
-  static ZS_HD int acc_row(int q, int v) { return 4 * v + q; }
+template <typename T>
+struct MatvarCap {
+  static constexpr int MAX_DIM = sizeof(T) == 4 ? ZS_MATVAR_MAX_DIM_F32 : ZS_MATVAR_MAX_DIM_F64;
 };
 
 ZS_HD int matvar_max_dim(int elem_bytes) { return elem_bytes == 4 ? ZS_MATVAR_MAX_DIM_F32 : (elem_bytes == 8 ? ZS_MATVAR_MAX_DIM_F64 : 0); }
-ZS_HD int matvar_blocks(int d) { return (d + 15) / 16; }
-ZS_HD int matvar_ld(int p) { return 16 * matvar_blocks(p) + ZS_MATVAR_PAD; }
+ZS_HD int matvar_ld(int p) { return 16 * blocks16(p) + ZS_MATVAR_PAD; }
 // elements of LDS: two tiles, the inverses of the diagonal blocks of U and of V, four reduction slots
 ZS_HD int64_t matvar_lds_elems(int n, int p) {
-  return 2 * (int64_t)(16 * matvar_blocks(n)) * matvar_ld(p) + 256 * (int64_t)(matvar_blocks(n) + matvar_blocks(p)) + 4;
+  return 2 * (int64_t)(16 * blocks16(n)) * matvar_ld(p) + 256 * (int64_t)(blocks16(n) + blocks16(p)) + 4;
 }
 
 // The backwards cut a row's K particles into `shares` contiguous runs of `per` particles; a workgroup walks one run in ascending

@@ -5,7 +5,7 @@
 // broadcast form even [R, C, D]), reduces them in a second pass and keeps them for the backward; here a score tile lives in the
 // accumulator registers of v_mfma_{f32,f64}_16x16x4 and only lp, dx and partials of the thin parameter gradients reach memory.
 // One template over the element type: the two instructions have the same operand layout and differ in the row map of the
-// accumulator (MixTile<T>::acc_row), in where the odd neighbour of an even output row lives (mix_odd_row) and in the panel width.
+// accumulator (MfmaTile<T>::acc_row), in where the odd neighbour of an even output row lives (mix_odd_row) and in the panel width.
 //
 // A lane l = 16 q + m of a wave holds, for the step s of a 16 x 16 tile, YY[row m][4 s + q] and Ws[4 s + q][component m] -- the
 // same two values serve the tile and its transpose, by the order of the instruction's operands:
@@ -26,39 +26,12 @@ namespace {
 
 constexpr int MIX_THREADS = 256;
 
-typedef float mix_f4 __attribute__((ext_vector_type(4)));
-typedef double mix_d4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct MixMfma;
-template <> struct MixMfma<float> {
-  typedef mix_f4 Acc;
-  static __device__ __forceinline__ Acc run(float a, float b, Acc c) {
-#if ZS_ON_DEVICE
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#else
-    return c;
-#endif
-  }
-  // out[n + 1] for the holder of an even output row n = 16 nt + acc_row(q, v): the next register of the same lane
-  static __device__ __forceinline__ float odd_row(const Acc& d, int v) { return d[v | 1]; }
-  static __device__ __forceinline__ bool holds_even(int q, int v) { return (v & 1) == 0; }
-};
-template <> struct MixMfma<double> {
-  typedef mix_d4 Acc;
-  static __device__ __forceinline__ Acc run(double a, double b, Acc c) {
-#if ZS_ON_DEVICE
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-#else
-    return c;
-#endif
-  }
-  // ... the same register of the lane q + 1 (every lane of the wave makes the exchange)
-  static __device__ __forceinline__ double odd_row(const Acc& d, int v) { return __shfl_xor(d[v], 16, ZS_WAVE); }
-  static __device__ __forceinline__ bool holds_even(int q, int v) { return (q & 1) == 0; }
-};
-
+// out[n + 1] for the holder of an even output row n = 16 nt + acc_row(q, v) -- f32: the next register of the same lane; f64: the
+// same register of the lane q ^ 1 (every lane of the wave makes the exchange)
+__device__ __forceinline__ float mix_odd_row(const Mfma<float>::Acc& d, int v) { return d[v | 1]; }
+__device__ __forceinline__ double mix_odd_row(const Mfma<double>::Acc& d, int v) { return __shfl_xor(d[v], 16, ZS_WAVE); }
 template <typename T>
-__device__ __forceinline__ T neg_inf() { return -(T)INFINITY; }
+__device__ __forceinline__ bool mix_holds_even(int q, int v) { return (MfmaTile<T>::acc_row(q, v) & 1) == 0; }
 
 // ---------------------------------------------------------------- the prologue
 // blocks [0, D): the centre of a dimension;  block D: the log-sum-exp of the logits
@@ -114,12 +87,12 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_pack(const T* __restrict__ 
   w.b[c] = live ? ((lsm - sum_ls) - (T)(0.5 * ZS_MIX_LOG_2PI) * (T)D) - (T)0.5 * sum_q : neg_inf<T>();
 }
 
-// ---------------------------------------------------------------- staging and the tile
+// ---------------------------------------------------------------- staging (the tile product is zs_tile_math.h's panel_tile)
 // Ws[k][j] = W[k, col0 + j] for k < K16, bs[j] = b[col0 + j] (-inf past the last component).  Every thread of the workgroup
 // calls it; the panel is ready when it returns.
 template <typename T>
 __device__ __forceinline__ void mix_stage_panel(const MixPrep<T>& w, int K16, int64_t col0, T* Ws, T* bs) {
-  constexpr int P = MixTile<T>::PANEL, LD = MixTile<T>::LD;
+  constexpr int P = MfmaPanel<T>::PANEL, LD = MfmaPanel<T>::LD;
   const int n = K16 * P, threads = blockDim.x;
   __syncthreads();          // the previous panel's readers are done
   for (int i = threadIdx.x; i < n; i += threads) {
@@ -141,39 +114,19 @@ __device__ __forceinline__ void mix_load_rows(const T* __restrict__ x, const T* 
   }
 }
 
-// one 16 x 16 tile of YY @ Ws over the 16 components at Wc = Ws + (first component of the tile); ROWS_FIRST: see the head of the file
-template <typename T, bool ROWS_FIRST>
-__device__ __forceinline__ typename MixMfma<T>::Acc mix_tile(const T (&a)[ZS_MIX_MAX_STEPS], const T* Wc, int q, int m, int steps) {
-  constexpr int LD = MixTile<T>::LD;
-  typename MixMfma<T>::Acc acc = {0, 0, 0, 0};
-#pragma unroll
-  for (int s = 0; s < ZS_MIX_MAX_STEPS; ++s) {
-    if (s < steps) {          // (uniform; a break would keep the loop, and a[], from unrolling into registers)
-      const T b = Wc[(4 * s + q) * LD + m];
-      acc = ROWS_FIRST ? MixMfma<T>::run(a[s], b, acc) : MixMfma<T>::run(b, a[s], acc);
-    }
-  }
-  return acc;
-}
-
 template <typename T>
-__device__ __forceinline__ T* mix_lds() {
-  extern __shared__ __align__(16) unsigned char mix_lds_bytes[];
-  return reinterpret_cast<T*>(mix_lds_bytes);
-}
-template <typename T>
-size_t mix_lds_bytes_for(int K16) { return sizeof(T) * (size_t)(K16 * MixTile<T>::LD + MixTile<T>::PANEL); }
+size_t mix_lds_bytes_for(int K16) { return sizeof(T) * (size_t)(K16 * MfmaPanel<T>::LD + MfmaPanel<T>::PANEL); }
 
 // ---------------------------------------------------------------- lp
 template <typename T>
 __global__ __launch_bounds__(MIX_THREADS) void k_mix_logprob(const T* __restrict__ x, const T* __restrict__ prep, T* __restrict__ lp,
                                                              int64_t R, int64_t C, int D) {
-  constexpr int P = MixTile<T>::PANEL;
+  constexpr int P = MfmaPanel<T>::PANEL;
   const int K16 = mix_k16(D), steps = mix_steps(D);
   const MixPrep<T> w = mix_prep(const_cast<T*>(prep), C, D);
-  T* Ws = mix_lds<T>();
-  T* bs = Ws + K16 * MixTile<T>::LD;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6, m = lane & 15, q = lane >> 4;
+  T* Ws = tile_lds<T>();
+  T* bs = Ws + K16 * MfmaPanel<T>::LD;
+  const int wave = mfma_wave(threadIdx.x), waves = blockDim.x >> 6, m = mfma_m(threadIdx.x), q = mfma_q(threadIdx.x);
   const int64_t r = ((int64_t)blockIdx.x * waves + wave) * 16 + m;
   const bool live = r < R;
   T a[ZS_MIX_MAX_STEPS];
@@ -186,11 +139,11 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_logprob(const T* __restrict
 #pragma unroll
     for (int ct = 0; ct < P / 16; ++ct) {
       if (col0 + ct * 16 < C) {
-        const typename MixMfma<T>::Acc acc = mix_tile<T, false>(a, Ws + ct * 16, q, m, steps);
+        const typename Mfma<T>::Acc acc = panel_tile<T, false>(a, Ws + ct * 16, q, m, steps);
         T s[4], tm = neg_inf<T>();
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          s[v] = acc[v] + bs[ct * 16 + MixTile<T>::acc_row(q, v)];
+          s[v] = acc[v] + bs[ct * 16 + MfmaTile<T>::acc_row(q, v)];
           tm = max_of(tm, s[v]);
         }
         mix_fold(mx, sm, s, tm);
@@ -209,13 +162,13 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_logprob(const T* __restrict
 template <typename T>
 __global__ __launch_bounds__(MIX_THREADS) void k_mix_grad_x(const T* __restrict__ x, const T* __restrict__ g, const T* __restrict__ lp,
                                                             const T* __restrict__ prep, T* __restrict__ dx, int64_t R, int64_t C, int D) {
-  constexpr int P = MixTile<T>::PANEL, LD = MixTile<T>::LD;
-  typedef typename MixMfma<T>::Acc Acc;
+  constexpr int P = MfmaPanel<T>::PANEL, LD = MfmaPanel<T>::LD;
+  typedef typename Mfma<T>::Acc Acc;
   const int K16 = mix_k16(D), steps = mix_steps(D), ntiles = K16 / 16;
   const MixPrep<T> w = mix_prep(const_cast<T*>(prep), C, D);
-  T* Ws = mix_lds<T>();
+  T* Ws = tile_lds<T>();
   T* bs = Ws + K16 * LD;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6, m = lane & 15, q = lane >> 4;
+  const int wave = mfma_wave(threadIdx.x), waves = blockDim.x >> 6, m = mfma_m(threadIdx.x), q = mfma_q(threadIdx.x);
   const int64_t r = ((int64_t)blockIdx.x * waves + wave) * 16 + m;
   const bool live = r < R;
   const int64_t rc = live ? r : R - 1;
@@ -232,16 +185,16 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_grad_x(const T* __restrict_
 #pragma unroll
     for (int ct = 0; ct < P / 16; ++ct) {
       if (col0 + ct * 16 < C) {
-        const Acc acc = mix_tile<T, false>(a, Ws + ct * 16, q, m, steps);
+        const Acc acc = panel_tile<T, false>(a, Ws + ct * 16, q, m, steps);
         T G[4];
 #pragma unroll
-        for (int v = 0; v < 4; ++v) G[v] = mix_weight(live, gr, acc[v] + bs[ct * 16 + MixTile<T>::acc_row(q, v)], lpr);
+        for (int v = 0; v < 4; ++v) G[v] = mix_weight(live, gr, acc[v] + bs[ct * 16 + MfmaTile<T>::acc_row(q, v)], lpr);
 #pragma unroll
         for (int nt = 0; nt < ZS_MIX_MAX_NTILES; ++nt) {
           if (nt < ntiles) {
 #pragma unroll
             for (int v = 0; v < 4; ++v)
-              d[nt] = MixMfma<T>::run(Ws[(nt * 16 + m) * LD + ct * 16 + MixTile<T>::acc_row(q, v)], G[v], d[nt]);
+              d[nt] = Mfma<T>::run(Ws[(nt * 16 + m) * LD + ct * 16 + MfmaTile<T>::acc_row(q, v)], G[v], d[nt]);
           }
         }
       }
@@ -253,9 +206,9 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_grad_x(const T* __restrict_
     if (nt < ntiles) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const T odd = MixMfma<T>::odd_row(d[nt], v);
-        const int dim = (nt * 16 + MixTile<T>::acc_row(q, v)) >> 1;
-        if (MixMfma<T>::holds_even(q, v) && live && dim < D) {
+        const T odd = mix_odd_row(d[nt], v);
+        const int dim = (nt * 16 + MfmaTile<T>::acc_row(q, v)) >> 1;
+        if (mix_holds_even<T>(q, v) && live && dim < D) {
           const T y = x[r * D + dim] - w.cen[dim];
           dx[r * D + dim] = d[nt][v] + (T)2 * y * odd;
         }
@@ -269,16 +222,16 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_grad_x(const T* __restrict_
 template <typename T>
 __global__ __launch_bounds__(MIX_THREADS) void k_mix_grad_params(const T* __restrict__ x, const T* __restrict__ g, const T* __restrict__ lp,
                                                                  const T* __restrict__ prep, T* __restrict__ part, int64_t R, int64_t C, int D) {
-  constexpr int P = MixTile<T>::PANEL, LD = MixTile<T>::LD;
-  typedef typename MixMfma<T>::Acc Acc;
+  constexpr int P = MfmaPanel<T>::PANEL, LD = MfmaPanel<T>::LD;
+  typedef typename Mfma<T>::Acc Acc;
   const int K16 = mix_k16(D), steps = mix_steps(D), ntiles = K16 / 16;
   const MixPrep<T> w = mix_prep(const_cast<T*>(prep), C, D);
-  T* Ws = mix_lds<T>();
+  T* Ws = tile_lds<T>();
   T* bs = Ws + K16 * LD;
   const int64_t col0 = (int64_t)blockIdx.x * P, share = blockIdx.y, shares = gridDim.y;
   mix_stage_panel(w, K16, col0, Ws, bs);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, q = lane >> 4;
-  const int64_t col = col0 + wave * 16 + m, tiles = mix_row_tiles(R);
+  const int wave = mfma_wave(threadIdx.x), m = mfma_m(threadIdx.x), q = mfma_q(threadIdx.x);
+  const int64_t col = col0 + wave * 16 + m, tiles = blocks16(R);
   const T* Wc = Ws + wave * 16;
   const T bc = bs[wave * 16 + m];
   Acc acc_out[ZS_MIX_MAX_NTILES];          // acc_out[nt][v] = sum_r YY[r][16 nt + acc_row(q, v)] G[r][component m]
@@ -290,12 +243,12 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_grad_params(const T* __rest
     for (int64_t rt = share; rt < tiles; rt += shares) {
       const int64_t ra = rt * 16 + m;
       mix_load_rows(x, w.cen, D, ra < R ? ra : R - 1, q, a);
-      const Acc acc = mix_tile<T, true>(a, Wc, q, m, steps);
+      const Acc acc = panel_tile<T, true>(a, Wc, q, m, steps);
       T G[4];
       int64_t rows[4];
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int64_t r = rt * 16 + MixTile<T>::acc_row(q, v);
+        const int64_t r = rt * 16 + MfmaTile<T>::acc_row(q, v);
         const bool live = r < R;
         rows[v] = live ? r : R - 1;
         const T gr = live ? g[rows[v]] : (T)0;
@@ -310,7 +263,7 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_grad_params(const T* __rest
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
             const T yy = dim < D ? mix_row_elem(x[rows[v] * D + dim] - w.cen[dim], k) : (T)0;
-            acc_out[nt] = MixMfma<T>::run(yy, G[v], acc_out[nt]);
+            acc_out[nt] = Mfma<T>::run(yy, G[v], acc_out[nt]);
           }
         }
       }
@@ -321,7 +274,7 @@ __global__ __launch_bounds__(MIX_THREADS) void k_mix_grad_params(const T* __rest
   for (int nt = 0; nt < ZS_MIX_MAX_NTILES; ++nt) {
     if (nt < ntiles) {
 #pragma unroll
-      for (int v = 0; v < 4; ++v) out[(int64_t)(nt * 16 + MixTile<T>::acc_row(q, v)) * w.cpad + col] = acc_out[nt][v];
+      for (int v = 0; v < 4; ++v) out[(int64_t)(nt * 16 + MfmaTile<T>::acc_row(q, v)) * w.cpad + col] = acc_out[nt][v];
     }
   }
   nsum += __shfl_xor(nsum, 16, ZS_WAVE);          // over the 16 rows of the tiles: q = 0 .. 3
@@ -410,9 +363,9 @@ int mix_grad_params(const void* x, const void* g, const void* lp, const void* me
                     void* dlogits, void* dmean, void* dlogstd, int64_t R, int64_t C, int64_t D, int64_t shares, void* stream) {
   const int rc = mix_check(x && g && lp && mean && logstd && prep && part && dlogits && dmean && dlogstd, R, C, D);
   if (rc) return rc == 1 ? 0 : rc;          // (R == 0 before the shares: zs_mix_row_shares has none to offer for no rows)
-  if (shares < 1 || shares > mix_row_tiles(R) || shares > 65535) return ZS_EINVAL;
-  const int waves = MixTile<T>::PANEL / 16;
-  hipLaunchKernelGGL((k_mix_grad_params<T>), dim3((unsigned)mix_panels(sizeof(T), C), (unsigned)shares), dim3(64 * waves),
+  if (shares < 1 || shares > blocks16(R) || shares > 65535) return ZS_EINVAL;
+  const int waves = MfmaPanel<T>::PANEL / 16;
+  hipLaunchKernelGGL((k_mix_grad_params<T>), dim3((unsigned)panels(sizeof(T), C), (unsigned)shares), dim3(64 * waves),
                      mix_lds_bytes_for<T>(mix_k16(D)), (hipStream_t)stream, (const T*)x, (const T*)g, (const T*)lp, (const T*)prep, (T*)part,
                      R, C, (int)D);
   ZS_CHECK_LAUNCH();
@@ -427,10 +380,10 @@ int mix_grad_params(const void* x, const void* g, const void* lp, const void* me
 extern "C" int zs_mix_abi_version(void) { return ZS_MIX_ABI_VERSION; }
 extern "C" int zs_mix_max_dim(void) { return ZS_MIX_MAX_DIM; }
 extern "C" int zs_mix_max_components(void) { return ZS_MIX_MAX_COMPONENTS; }
-extern "C" int64_t zs_mix_panels(int elem_bytes, int64_t C) { return mix_panels(elem_bytes, C); }
+extern "C" int64_t zs_mix_panels(int elem_bytes, int64_t C) { return panels(elem_bytes, C); }
 extern "C" int64_t zs_mix_row_shares(int elem_bytes, int64_t R, int64_t C) { return mix_row_shares(elem_bytes, R, C); }
 extern "C" int64_t zs_mix_workspace_elems(int which, int elem_bytes, int64_t C, int64_t D, int64_t shares) {
-  if (mix_panels(elem_bytes, C) == 0 || C > ZS_MIX_MAX_COMPONENTS || D < 1 || D > ZS_MIX_MAX_DIM) return -1;
+  if (panels(elem_bytes, C) == 0 || C > ZS_MIX_MAX_COMPONENTS || D < 1 || D > ZS_MIX_MAX_DIM) return -1;
   switch (which) {
     case ZS_MIX_WS_PREP: return mix_prep_elems(elem_bytes, C, D);
     case ZS_MIX_WS_GRAD_PARAMS: return shares < 1 ? -1 : mix_part_elems(elem_bytes, C, D, shares);

@@ -1,11 +1,13 @@
-// The arithmetic of the mixture-of-Gaussians density (include/zs_mix.h) that is not scheduling: the tile geometry of the two
-// matrix instructions, the sizes and the layout of the workspaces, the split of the grad_params grid, and the per-element
-// expressions of the prologue, the epilogues and the finish.  __host__ __device__ like the other *_math.h headers; zs_mix.hip
-// only stages, multiplies and reduces.
+// The arithmetic of the mixture-of-Gaussians density (include/zs_mix.h) that is not scheduling: the interleaved operand, the
+// sizes and the layout of the workspaces, the split of the grad_params grid, and the per-element expressions of the prologue,
+// the epilogues and the finish; the tile of the two matrix instructions, its row map and the staged panel are zs_tile_math.h's
+// (MfmaTile, MfmaPanel, panel_tile).  __host__ __device__ like the other *_math.h headers; zs_mix.hip only stages, multiplies
+// and reduces.
 #pragma once
 #include "zs_common.h"
 #include "zs_flat_math.h"
 #include "zs_group_math.h"
+#include "zs_tile_math.h"
 
 #define ZS_MIX_MAX_DIM 64
 #define ZS_MIX_MAX_COMPONENTS 65536
@@ -17,34 +19,16 @@
 
 namespace zs {
 
-// v_mfma_*_16x16x4: lane l = 16 q + m holds A[i = m][k = q], B[k = q][j = m] and four values D[acc_row(q, v)][j = m]; the f32
-// instruction gives a lane four consecutive rows, the f64 one every fourth row (as zs_topic_math.h).  The k axis of the packed
-// operand interleaves the two halves of [y | y^2] -- k = 2 d and 2 d + 1 --, so that the two output rows a gradient element
-// needs are neighbours: in one lane (f32: v and v + 1) or in the lanes q and q + 1 (f64).  A row of the staged panel is padded
-// by 17 elements so that the four k rows a matrix step reads fall into different banks.
-template <typename T> struct MixTile;
-template <> struct MixTile<float> {
-  static constexpr int PANEL = 64, LD = PANEL + 17;
-  static ZS_HD int acc_row(int q, int v) { return 4 * q + v; }
-};
-template <> struct MixTile<double> {
-  static constexpr int PANEL = 32, LD = PANEL + 17;
-  static ZS_HD int acc_row(int q, int v) { return 4 * v + q; }
-};
-
-ZS_HD int mix_panel_cols(int elem_bytes) { return elem_bytes == 4 ? MixTile<float>::PANEL : (elem_bytes == 8 ? MixTile<double>::PANEL : 0); }
-ZS_HD int mix_k16(int64_t D) { return (int)((2 * D + 15) / 16 * 16); }          // rows of the staged panel
+// The k axis of the packed operand interleaves the two halves of [y | y^2] -- k = 2 d and 2 d + 1 --, so that the two output
+// rows a gradient element needs are the neighbours of zs_tile_math.h's row map: in one lane (f32) or in the lanes q and q ^ 1
+// (f64).
+ZS_HD int mix_k16(int64_t D) { return (int)(blocks16(2 * D) * 16); }          // rows of the staged panel
 ZS_HD int mix_steps(int64_t D) { return (int)((2 * D + 3) / 4); }
-ZS_HD int64_t mix_panels(int elem_bytes, int64_t C) {
-  const int p = mix_panel_cols(elem_bytes);
-  return (p == 0 || C < 1) ? 0 : (C + p - 1) / p;
-}
-ZS_HD int64_t mix_cpad(int elem_bytes, int64_t C) { return mix_panels(elem_bytes, C) * mix_panel_cols(elem_bytes); }
-ZS_HD int64_t mix_row_tiles(int64_t R) { return (R + 15) / 16; }
+ZS_HD int64_t mix_cpad(int elem_bytes, int64_t C) { return panels(elem_bytes, C) * panel_cols(elem_bytes); }
 ZS_HD int64_t mix_row_shares(int elem_bytes, int64_t R, int64_t C) {
-  const int64_t panels = mix_panels(elem_bytes, C);
+  const int64_t panels = zs::panels(elem_bytes, C);
   if (panels == 0 || R < 1) return 0;
-  const int64_t s = (ZS_MIX_GRID_TARGET + panels - 1) / panels, tiles = mix_row_tiles(R);
+  const int64_t s = (ZS_MIX_GRID_TARGET + panels - 1) / panels, tiles = blocks16(R);
   return s > tiles ? tiles : s;
 }
 

@@ -32,31 +32,6 @@ constexpr int SLAB = ZS_SVGD_SLAB;
 constexpr int LDG = ZS_SVGD_LD_GRAM;
 constexpr int LDU = ZS_SVGD_LD_UPDATE;
 
-typedef float svgd_f4 __attribute__((ext_vector_type(4)));
-typedef double svgd_d4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct Mfma;
-template <> struct Mfma<float> {
-  typedef svgd_f4 Acc;
-  static __device__ __forceinline__ Acc run(float a, float b, Acc c) {
-#if ZS_ON_DEVICE
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#else
-    return c;
-#endif
-  }
-};
-template <> struct Mfma<double> {
-  typedef svgd_d4 Acc;
-  static __device__ __forceinline__ Acc run(double a, double b, Acc c) {
-#if ZS_ON_DEVICE
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-#else
-    return c;
-#endif
-  }
-};
-
 template <typename T>
 struct Table {
   const T* q[ZS_SVGD_MAX_TENSORS];
@@ -110,11 +85,11 @@ __global__ __launch_bounds__(ZS_SVGD_GRAM_THREADS) void k_svgd_gram(const Table<
                                                                     double* partials) {
   typedef typename Mfma<T>::Acc Acc;
   constexpr int THREADS = ZS_SVGD_GRAM_THREADS, PARTS = THREADS / SLAB;
-  __shared__ T tile[SvgdTile<T>::MAX_K * LDG];
+  __shared__ T tile[SvgdCap<T>::MAX_K * LDG];
   __shared__ T red[PARTS * SLAB];
   __shared__ T mean[SLAB];
   const int nb = svgd_blocks(K), npairs = svgd_pairs(nb), k16 = 16 * nb;
-  const int lane = threadIdx.x & 63, m = lane & 15, q = lane >> 4, wave = threadIdx.x >> 6;
+  const int m = mfma_m(threadIdx.x), q = mfma_q(threadIdx.x), wave = mfma_wave(threadIdx.x);
   const int c = threadIdx.x % SLAB, part = threadIdx.x / SLAB;
   int bi[PPW], bj[PPW];
   Acc acc[PPW];
@@ -156,7 +131,7 @@ __global__ __launch_bounds__(ZS_SVGD_GRAM_THREADS) void k_svgd_gram(const Table<
     if (svgd_pair_index(wave, t) < npairs) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int r = 16 * bi[t] + SvgdTile<T>::acc_row(q, v), cc = 16 * bj[t] + m;
+        const int r = 16 * bi[t] + MfmaTile<T>::acc_row(q, v), cc = 16 * bj[t] + m;
         if (r < K && cc < K) {
           out[r * K + cc] = (double)acc[t][v];
           if (bi[t] != bj[t]) out[cc * K + r] = (double)acc[t][v];
@@ -246,7 +221,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_svgd_update(const Table<T> ts, i
   __shared__ T mean[SLAB];
   __shared__ T rowsum[16 * NB];
   const int nb = svgd_blocks(K), k16 = 16 * nb, ksteps = 4 * nb;
-  const int lane = threadIdx.x & 63, m = lane & 15, q = lane >> 4, wave = threadIdx.x >> 6;
+  const int m = mfma_m(threadIdx.x), q = mfma_q(threadIdx.x), wave = mfma_wave(threadIdx.x);
   const int c = threadIdx.x % SLAB, part = threadIdx.x / SLAB;
   const bool owner = wave < nb;
   SvgdStep<T> st = st0;
@@ -291,7 +266,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_svgd_update(const Table<T> ts, i
           const T mu = mean[cc];
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
-            const int r = 16 * wave + SvgdTile<T>::acc_row(q, v);
+            const int r = 16 * wave + MfmaTile<T>::acc_row(q, v);
             if (r < K) {
               const int64_t at = (int64_t)r * w.width + w.off;
               const T theta = ts.q[w.t][at];
@@ -311,7 +286,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_svgd_update(const Table<T> ts, i
 template <typename T>
 int fill_table(bool update, bool adagrad, const zs_svgd_tensor* tensors, int n_tensors, int64_t n, int64_t K, Table<T>& ts) {
   if (!tensors || n_tensors < 1 || K < 1 || n < 0) return ZS_EINVAL;
-  if (n_tensors > ZS_SVGD_MAX_TENSORS || K > SvgdTile<T>::MAX_K) return ZS_ENOTSUP;
+  if (n_tensors > ZS_SVGD_MAX_TENSORS || K > SvgdCap<T>::MAX_K) return ZS_ENOTSUP;
   memset(&ts, 0, sizeof(ts));
   ts.n_tensors = n_tensors;
   int64_t col = 0;
@@ -347,7 +322,7 @@ int svgd_gram(const zs_svgd_tensor* tensors, int n_tensors, int64_t n, int64_t K
   hipStream_t st = (hipStream_t)stream;
   if (ppw <= 1) launch_gram<T, 1>(grid, st, ts, D, (int)K, slabs, partials);
   else if (ppw <= 5) launch_gram<T, 5>(grid, st, ts, D, (int)K, slabs, partials);
-  else if constexpr (SvgdTile<T>::MAX_K > 128) launch_gram<T, 17>(grid, st, ts, D, (int)K, slabs, partials);
+  else if constexpr (SvgdCap<T>::MAX_K > 128) launch_gram<T, 17>(grid, st, ts, D, (int)K, slabs, partials);
   ZS_CHECK_LAUNCH();
   return 0;
 }
@@ -383,7 +358,7 @@ int svgd_update(const zs_svgd_tensor* tensors, int n_tensors, int64_t n, int64_t
   hipStream_t st = (hipStream_t)stream;
   if (nb <= 2) launch_update<T, 2, 4>(st, ts, D, (int)K, state, step);
   else if (nb <= 8) launch_update<T, 8, 8>(st, ts, D, (int)K, state, step);
-  else if constexpr (SvgdTile<T>::MAX_K > 128) launch_update<T, 16, 16>(st, ts, D, (int)K, state, step);
+  else if constexpr (SvgdCap<T>::MAX_K > 128) launch_update<T, 16, 16>(st, ts, D, (int)K, state, step);
   ZS_CHECK_LAUNCH();
   return 0;
 }

@@ -1,10 +1,11 @@
-// The arithmetic of Stein variational gradient descent (include/zs_svgd.h) that is not scheduling: the geometry of the matrix
-// instruction, the deal of the Gram matrix's tile pairs over the waves, the padded-row mask, the bit-pattern selection of the
+// The arithmetic of Stein variational gradient descent (include/zs_svgd.h) that is not scheduling: the leading dimensions of the
+// LDS tiles (the lanes' places in them: zs_tile_math.h), the deal of the Gram matrix's tile pairs over the waves, the padded-row mask, the bit-pattern selection of the
 // median, the bandwidth and the per-element step.  __host__ __device__ like the other *_math.h headers
 // (tests/host_math/zs_svgd_host_math.hip runs it on the host); zs_svgd.hip only stages, multiplies and reduces.
 #pragma once
 #include "zs_common.h"
 #include "zs_flat_math.h"
+#include "zs_tile_math.h"
 #include "../../include/zs_svgd.h"
 
 #define ZS_SVGD_GRAM_WAVES 8
@@ -12,7 +13,8 @@
 #define ZS_SVGD_FINISH_THREADS 1024
 // Leading dimensions of the LDS tiles.  Gram: both operands are read along a row, lane 16 q + m at m LD + 4 s + q; LD = 36 is four
 // times an odd number, so the 64 lanes fall into 64 different 4-byte banks.  Update: the B operand is read down a column, lane
-// 16 q + m at (4 s + q) LD + 16 cb + m; with LD = 48 the four k-rows start 48 banks apart: 0, 48, 32, 16.
+// 16 q + m at (4 s + q) LD + 16 cb + m; with LD = 48 the four k-rows start 48 banks apart: 0, 48, 32, 16.  (float32; the words
+// of a float64 step fall into every bank twice, the least possible, with either.)
 #define ZS_SVGD_LD_GRAM (ZS_SVGD_SLAB + 4)
 #define ZS_SVGD_LD_UPDATE (ZS_SVGD_SLAB + 16)
 // LDS (bytes; the tile, THREADS / 32 x 32 column-sum partials, 32 means, update: the row sums):
@@ -21,22 +23,15 @@
 
 namespace zs {
 
-// v_mfma_*_16x16x4: lane l = 16 q + m holds A[i = m][k = q], B[k = q][j = m] and four values D[acc_row(q, v)][j = m]; the f32
-// instruction gives a lane four consecutive rows, the f64 one every fourth row (zs_matvar_math.h, restated).
-template <typename T> struct SvgdTile;
-template <> struct SvgdTile<float> {
-  static constexpr int MAX_K = ZS_SVGD_MAX_PARTICLES;
-  static ZS_HD int acc_row(int q, int v) { return 4 * q + v; }
-};
-template <> struct SvgdTile<double> {
-  static constexpr int MAX_K = ZS_SVGD_MAX_PARTICLES_F64;
-  static ZS_HD int acc_row(int q, int v) { return 4 * v + q; }
+template <typename T>
+struct SvgdCap {
+  static constexpr int MAX_K = sizeof(T) == 4 ? ZS_SVGD_MAX_PARTICLES : ZS_SVGD_MAX_PARTICLES_F64;
 };
 
 ZS_HD int svgd_max_particles_of(int elem_bytes) {
   return elem_bytes == 4 ? ZS_SVGD_MAX_PARTICLES : (elem_bytes == 8 ? ZS_SVGD_MAX_PARTICLES_F64 : 0);
 }
-ZS_HD int svgd_blocks(int K) { return (K + 15) / 16; }
+ZS_HD int svgd_blocks(int K) { return blocks16(K); }          // blocks of 16 particles
 ZS_HD bool svgd_row_live(int row, int K) { return row < K; }          // rows K .. 16 blocks(K) of a tile are zero
 ZS_HD int64_t svgd_slabs(int64_t D) { return (D + ZS_SVGD_SLAB - 1) / ZS_SVGD_SLAB; }
 ZS_HD int64_t svgd_gram_slots(int64_t D) {

@@ -6,7 +6,7 @@
 // the accumulator registers of v_mfma_{f32,f64}_16x16x4 tile by tile and only row sums and two thin gradients reach memory.
 // Operands are shifted to (0, 1] (zs_topic.h) so that the matrix instructions multiply plain numbers.  One template over the
 // element type: the two instructions have the same operand layout and differ in the row map of the accumulator
-// (TopicTile<T>::acc_row) and in the width of a panel.
+// (MfmaTile<T>::acc_row) and in the width of a panel.
 //
 // A lane l = 16 q + m of a wave holds, for the step s of a 16 x 16 tile, E[row m][4 s + q] and Bs[4 s + q][column m] -- the
 // same two values serve the tile and its transpose, by the order of the instruction's operands:
@@ -26,34 +26,6 @@ using namespace zs;
 namespace {
 
 constexpr int TOPIC_THREADS = 256;
-
-typedef float topic_f4 __attribute__((ext_vector_type(4)));
-typedef double topic_d4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct TopicMfma;
-template <> struct TopicMfma<float> {
-  typedef topic_f4 Acc;
-  static __device__ __forceinline__ Acc run(float a, float b, Acc c) {
-#if ZS_ON_DEVICE
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#else
-    return c;
-#endif
-  }
-};
-template <> struct TopicMfma<double> {
-  typedef topic_d4 Acc;
-  static __device__ __forceinline__ Acc run(double a, double b, Acc c) {
-#if ZS_ON_DEVICE
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-#else
-    return c;
-#endif
-  }
-};
-
-template <typename T>
-__device__ __forceinline__ T neg_inf() { return -(T)INFINITY; }
 
 // ---------------------------------------------------------------- the prologue
 // blocks [0, K): lse of a row of B;  then a wave per row of H: E, Z, log Z;  then a wave per row of X: N
@@ -101,13 +73,13 @@ __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_prepare(const T* __rest
   }
 }
 
-// ---------------------------------------------------------------- staging and the tile
+// ---------------------------------------------------------------- staging (the tile product is zs_tile_math.h's panel_tile)
 // Bs[k][j] = exp(B[k, col0 + j] - lse_k - c_j) for k < K16 (zero for k >= K and past the last column), cs[j] = c_j.
 // Every thread of the workgroup calls it; the panel is ready when it returns.
 template <typename T>
 __device__ __forceinline__ void topic_stage_panel(const T* __restrict__ B, const T* __restrict__ lse, int64_t V, int K, int K16,
                                                   int64_t col0, T* Bs, T* cs) {
-  constexpr int P = TopicTile<T>::PANEL, LD = TopicTile<T>::LD;
+  constexpr int P = MfmaPanel<T>::PANEL, LD = MfmaPanel<T>::LD;
   const int n = K16 * P, threads = blockDim.x;
   __syncthreads();          // the previous panel's readers are done
   for (int i = threadIdx.x; i < n; i += threads) {
@@ -138,44 +110,24 @@ __device__ __forceinline__ void topic_load_rows(const T* __restrict__ E, int K16
   for (int s = 0; s < ZS_TOPIC_MAX_STEPS; ++s) a[s] = s < steps ? E[row * K16 + 4 * s + q] : (T)0;
 }
 
-// one 16 x 16 tile of E @ Bs over the 16 columns at Bc = Bs + (first column of the tile); ROWS_FIRST: see the head of the file
-template <typename T, bool ROWS_FIRST>
-__device__ __forceinline__ typename TopicMfma<T>::Acc topic_tile(const T (&a)[ZS_TOPIC_MAX_STEPS], const T* Bc, int q, int m, int steps) {
-  constexpr int LD = TopicTile<T>::LD;
-  typename TopicMfma<T>::Acc acc = {0, 0, 0, 0};
-#pragma unroll
-  for (int s = 0; s < ZS_TOPIC_MAX_STEPS; ++s) {
-    if (s < steps) {          // (uniform; a break would keep the loop, and a[], from unrolling into registers)
-      const T b = Bc[(4 * s + q) * LD + m];
-      acc = ROWS_FIRST ? TopicMfma<T>::run(a[s], b, acc) : TopicMfma<T>::run(b, a[s], acc);
-    }
-  }
-  return acc;
-}
-
-template <typename T>
-__device__ __forceinline__ T* topic_lds() {
-  extern __shared__ __align__(16) unsigned char topic_lds_bytes[];
-  return reinterpret_cast<T*>(topic_lds_bytes);
-}
 template <typename T>
 size_t topic_lds_bytes_for(int64_t K16, int extra) {
-  return sizeof(T) * (size_t)(K16 * TopicTile<T>::LD + TopicTile<T>::PANEL + extra);
+  return sizeof(T) * (size_t)(K16 * MfmaPanel<T>::LD + MfmaPanel<T>::PANEL + extra);
 }
 
 // ---------------------------------------------------------------- lp
 template <typename T>
 __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_logprob(const T* __restrict__ B, const T* __restrict__ X, const T* __restrict__ prep,
                                                                  T* __restrict__ part, int64_t R, int K, int64_t V, int64_t Dx) {
-  constexpr int P = TopicTile<T>::PANEL, LD = TopicTile<T>::LD;
+  constexpr int P = MfmaPanel<T>::PANEL, LD = MfmaPanel<T>::LD;
   const int K16 = (int)topic_k16(K), steps = topic_steps(K);
   const TopicPrep<T> w = topic_prep(const_cast<T*>(prep), R, K, Dx);
-  T* Bs = topic_lds<T>();
+  T* Bs = tile_lds<T>();
   T* cs = Bs + K16 * LD;
   const int64_t panel = blockIdx.x, col0 = panel * P;
   topic_stage_panel(B, w.lse, V, K, K16, col0, Bs, cs);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6, m = lane & 15, q = lane >> 4;
-  const int64_t tiles = (R + 15) / 16;
+  const int wave = mfma_wave(threadIdx.x), waves = blockDim.x >> 6, m = mfma_m(threadIdx.x), q = mfma_q(threadIdx.x);
+  const int64_t tiles = blocks16(R);
   T a[ZS_TOPIC_MAX_STEPS];
   for (int64_t rt = wave; rt < tiles; rt += waves) {
     const int64_t r = rt * 16 + m;
@@ -187,10 +139,10 @@ __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_logprob(const T* __rest
 #pragma unroll
     for (int ct = 0; ct < P / 16; ++ct) {
       if (col0 + ct * 16 < V) {
-        const typename TopicMfma<T>::Acc acc = topic_tile<T, false>(a, Bs + ct * 16, q, m, steps);
+        const typename Mfma<T>::Acc acc = panel_tile<T, false>(a, Bs + ct * 16, q, m, steps);
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          const int j = ct * 16 + TopicTile<T>::acc_row(q, v);
+          const int j = ct * 16 + MfmaTile<T>::acc_row(q, v);
           const T x = (live && col0 + j < V) ? xr[col0 + j] : (T)0;
           sum += topic_term(x, cs[j], acc[v]);
         }
@@ -218,13 +170,13 @@ template <typename T>
 __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_grad_doc(const T* __restrict__ B, const T* __restrict__ X, const T* __restrict__ g,
                                                                   const T* __restrict__ prep, T* __restrict__ part, int64_t R, int K,
                                                                   int64_t V, int64_t Dx, int64_t panels) {
-  constexpr int P = TopicTile<T>::PANEL, LD = TopicTile<T>::LD;
-  typedef typename TopicMfma<T>::Acc Acc;
+  constexpr int P = MfmaPanel<T>::PANEL, LD = MfmaPanel<T>::LD;
+  typedef typename Mfma<T>::Acc Acc;
   const int K16 = (int)topic_k16(K), steps = topic_steps(K), ktiles = K16 / 16;
   const TopicPrep<T> w = topic_prep(const_cast<T*>(prep), R, K, Dx);
-  T* Bs = topic_lds<T>();
+  T* Bs = tile_lds<T>();
   T* cs = Bs + K16 * LD;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6, m = lane & 15, q = lane >> 4;
+  const int wave = mfma_wave(threadIdx.x), waves = blockDim.x >> 6, m = mfma_m(threadIdx.x), q = mfma_q(threadIdx.x);
   const int64_t r = ((int64_t)blockIdx.x * waves + wave) * 16 + m;
   const bool live = r < R;
   const int64_t rc = live ? r : R - 1;
@@ -242,11 +194,11 @@ __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_grad_doc(const T* __res
 #pragma unroll
     for (int ct = 0; ct < P / 16; ++ct) {
       if (col0 + ct * 16 < V) {
-        const Acc acc = topic_tile<T, false>(a, Bs + ct * 16, q, m, steps);
+        const Acc acc = panel_tile<T, false>(a, Bs + ct * 16, q, m, steps);
         T wgt[4];
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          const int64_t col = col0 + ct * 16 + TopicTile<T>::acc_row(q, v);
+          const int64_t col = col0 + ct * 16 + MfmaTile<T>::acc_row(q, v);
           const T x = (live && col < V) ? xr[col] : (T)0;
           wgt[v] = topic_weight(gr, x, acc[v]);
         }
@@ -255,7 +207,7 @@ __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_grad_doc(const T* __res
           if (kt < ktiles) {
 #pragma unroll
             for (int v = 0; v < 4; ++v)
-              d[kt] = TopicMfma<T>::run(Bs[(kt * 16 + m) * LD + ct * 16 + TopicTile<T>::acc_row(q, v)], wgt[v], d[kt]);
+              d[kt] = Mfma<T>::run(Bs[(kt * 16 + m) * LD + ct * 16 + MfmaTile<T>::acc_row(q, v)], wgt[v], d[kt]);
           }
         }
       }
@@ -267,7 +219,7 @@ __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_grad_doc(const T* __res
   for (int kt = 0; kt < ZS_TOPIC_MAX_KTILES; ++kt) {
     if (kt < ktiles) {
 #pragma unroll
-      for (int v = 0; v < 4; ++v) out[kt * 16 + TopicTile<T>::acc_row(q, v)] = d[kt][v];
+      for (int v = 0; v < 4; ++v) out[kt * 16 + MfmaTile<T>::acc_row(q, v)] = d[kt][v];
     }
   }
 }
@@ -293,17 +245,17 @@ template <typename T>
 __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_grad_topic(const T* __restrict__ B, const T* __restrict__ X, const T* __restrict__ g,
                                                                     const T* __restrict__ prep, T* __restrict__ part, T* __restrict__ dB,
                                                                     int64_t R, int K, int64_t V, int64_t Dx) {
-  constexpr int P = TopicTile<T>::PANEL, LD = TopicTile<T>::LD;
-  typedef typename TopicMfma<T>::Acc Acc;
+  constexpr int P = MfmaPanel<T>::PANEL, LD = MfmaPanel<T>::LD;
+  typedef typename Mfma<T>::Acc Acc;
   const int K16 = (int)topic_k16(K), steps = topic_steps(K), ktiles = K16 / 16;
   const TopicPrep<T> w = topic_prep(const_cast<T*>(prep), R, K, Dx);
-  T* Bs = topic_lds<T>();
+  T* Bs = tile_lds<T>();
   T* cs = Bs + K16 * LD;
   T* ss = cs + P;          // [waves][K16]: the waves' sums of T over their 16 columns
   const int64_t panel = blockIdx.x, col0 = panel * P;
   topic_stage_panel(B, w.lse, V, K, K16, col0, Bs, cs);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6, m = lane & 15, q = lane >> 4;
-  const int64_t col = col0 + wave * 16 + m, tiles = (R + 15) / 16;
+  const int wave = mfma_wave(threadIdx.x), waves = blockDim.x >> 6, m = mfma_m(threadIdx.x), q = mfma_q(threadIdx.x);
+  const int64_t col = col0 + wave * 16 + m, tiles = blocks16(R);
   const bool col_live = col < V;
   const T* Bc = Bs + wave * 16;
   Acc G[ZS_TOPIC_MAX_KTILES];
@@ -314,12 +266,12 @@ __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_grad_topic(const T* __r
     for (int64_t rt = 0; rt < tiles; ++rt) {
       const int64_t ra = rt * 16 + m;
       topic_load_rows(w.e, K16, ra < R ? ra : R - 1, q, steps, a);
-      const Acc acc = topic_tile<T, true>(a, Bc, q, m, steps);
+      const Acc acc = panel_tile<T, true>(a, Bc, q, m, steps);
       T wgt[4];
       int64_t rows[4];
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int64_t r = rt * 16 + TopicTile<T>::acc_row(q, v);
+        const int64_t r = rt * 16 + MfmaTile<T>::acc_row(q, v);
         const bool live = r < R && col_live;
         rows[v] = r < R ? r : R - 1;
         const T x = live ? X[mod_fast(rows[v], Dx) * V + col] : (T)0;
@@ -329,7 +281,7 @@ __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_grad_topic(const T* __r
       for (int kt = 0; kt < ZS_TOPIC_MAX_KTILES; ++kt) {
         if (kt < ktiles) {
 #pragma unroll
-          for (int v = 0; v < 4; ++v) G[kt] = TopicMfma<T>::run(w.e[rows[v] * K16 + kt * 16 + m], wgt[v], G[kt]);
+          for (int v = 0; v < 4; ++v) G[kt] = Mfma<T>::run(w.e[rows[v] * K16 + kt * 16 + m], wgt[v], G[kt]);
         }
       }
     }
@@ -340,7 +292,7 @@ __global__ __launch_bounds__(TOPIC_THREADS) void k_topic_grad_topic(const T* __r
     if (kt < ktiles) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int k = kt * 16 + TopicTile<T>::acc_row(q, v);
+        const int k = kt * 16 + MfmaTile<T>::acc_row(q, v);
         const T t = Bc[k * LD + m] * G[kt][v];
         if (k < K && col_live) dB[(int64_t)k * V + col] = t;
         const T row = group_sum(t, 16);          // over the wave's 16 columns
@@ -400,7 +352,7 @@ int topic_logprob(const void* B, const void* X, const void* prep, void* part, vo
                   void* stream) {
   const int rc = topic_check(B && X && prep && part && lp, R, K, V, Dx);
   if (rc) return rc == 1 ? 0 : rc;
-  const int64_t panels = topic_panels(sizeof(T), V);
+  const int64_t panels = zs::panels(sizeof(T), V);
   hipLaunchKernelGGL((k_topic_logprob<T>), dim3((unsigned)panels), dim3(TOPIC_THREADS), topic_lds_bytes_for<T>(topic_k16(K), 0),
                      (hipStream_t)stream, (const T*)B, (const T*)X, (const T*)prep, (T*)part, R, (int)K, V, Dx);
   ZS_CHECK_LAUNCH();
@@ -415,7 +367,7 @@ int topic_grad_doc(const void* B, const void* X, const void* g, const void* prep
                    int64_t Dx, int64_t splits, void* stream) {
   const int rc = topic_check(B && X && g && prep && part && dH, R, K, V, Dx);
   if (rc) return rc == 1 ? 0 : rc;          // (R == 0 before the splits: zs_topic_doc_splits has none to offer for no rows)
-  const int64_t panels = topic_panels(sizeof(T), V);
+  const int64_t panels = zs::panels(sizeof(T), V);
   if (splits < 1 || splits > panels || splits > 65535) return ZS_EINVAL;
   const int64_t row_blocks = (R + ZS_TOPIC_ROWS_PER_BLOCK - 1) / ZS_TOPIC_ROWS_PER_BLOCK;
   hipLaunchKernelGGL((k_topic_grad_doc<T>), dim3((unsigned)row_blocks, (unsigned)splits), dim3(TOPIC_THREADS),
@@ -433,8 +385,8 @@ int topic_grad_topic(const void* B, const void* X, const void* g, const void* pr
                      int64_t Dx, void* stream) {
   const int rc = topic_check(B && X && g && prep && part && dB, R, K, V, Dx);
   if (rc) return rc == 1 ? 0 : rc;
-  const int64_t panels = topic_panels(sizeof(T), V), K16 = topic_k16(K);
-  const int waves = TopicTile<T>::PANEL / 16;
+  const int64_t panels = zs::panels(sizeof(T), V), K16 = topic_k16(K);
+  const int waves = MfmaPanel<T>::PANEL / 16;
   hipLaunchKernelGGL((k_topic_grad_topic<T>), dim3((unsigned)panels), dim3(64 * waves), topic_lds_bytes_for<T>(K16, waves * (int)K16),
                      (hipStream_t)stream, (const T*)B, (const T*)X, (const T*)g, (const T*)prep, (T*)part, (T*)dB, R, (int)K, V, Dx);
   ZS_CHECK_LAUNCH();
@@ -448,10 +400,10 @@ int topic_grad_topic(const void* B, const void* X, const void* g, const void* pr
 
 extern "C" int zs_topic_abi_version(void) { return ZS_TOPIC_ABI_VERSION; }
 extern "C" int zs_topic_max_topics(void) { return ZS_TOPIC_MAX_TOPICS; }
-extern "C" int64_t zs_topic_panels(int elem_bytes, int64_t V) { return topic_panels(elem_bytes, V); }
+extern "C" int64_t zs_topic_panels(int elem_bytes, int64_t V) { return panels(elem_bytes, V); }
 extern "C" int64_t zs_topic_doc_splits(int elem_bytes, int64_t R, int64_t V) { return topic_doc_splits(elem_bytes, R, V); }
 extern "C" int64_t zs_topic_workspace_elems(int which, int elem_bytes, int64_t R, int64_t K, int64_t V, int64_t Dx, int64_t splits) {
-  const int64_t panels = topic_panels(elem_bytes, V);
+  const int64_t panels = zs::panels(elem_bytes, V);
   if (panels == 0 || R < 0 || K < 1 || K > ZS_TOPIC_MAX_TOPICS || Dx < 1) return -1;
   switch (which) {
     case ZS_TOPIC_WS_PREP: return topic_prep_elems(R, K, Dx);

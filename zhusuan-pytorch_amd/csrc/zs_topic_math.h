@@ -1,10 +1,12 @@
-// The arithmetic of the admixture likelihood (include/zs_topic.h) that is not scheduling: the tile geometry of the two matrix
-// instructions, the sizes and the layout of the workspaces, the split of the grad_doc grid, and the per-element expressions of
-// the epilogues.  __host__ __device__ like the other *_math.h headers; zs_topic.hip only stages, multiplies and reduces.
+// The arithmetic of the admixture likelihood (include/zs_topic.h) that is not scheduling: the sizes and the layout of the
+// workspaces, the split of the grad_doc grid, and the per-element expressions of the epilogues; the tile of the two matrix
+// instructions, its row map and the staged panel of B are zs_tile_math.h's (MfmaTile, MfmaPanel, panel_tile).  __host__
+// __device__ like the other *_math.h headers; zs_topic.hip only stages, multiplies and reduces.
 #pragma once
 #include "zs_common.h"
 #include "zs_flat_math.h"
 #include "zs_group_math.h"
+#include "zs_tile_math.h"
 
 #define ZS_TOPIC_MAX_TOPICS 128
 #define ZS_TOPIC_MAX_STEPS (ZS_TOPIC_MAX_TOPICS / 4)          // matrix instructions per 16 x 16 tile: the k axis in fours
@@ -14,29 +16,10 @@
 
 namespace zs {
 
-// v_mfma_*_16x16x4: lane l = 16 q + m holds A[i = m][k = q], B[k = q][j = m] and four values D[acc_row(q, v)][j = m].  The two
-// element types differ ONLY in acc_row: the f32 instruction gives a lane four consecutive rows, the f64 one every fourth row.
-// A panel is as many columns as keep the staged operand within 32 - 50 KB of LDS at 128 topics; a row of the panel is padded by
-// 17 elements so that the four k rows a matrix step reads fall into different banks.
-template <typename T> struct TopicTile;
-template <> struct TopicTile<float> {
-  static constexpr int PANEL = 64, LD = PANEL + 17;
-  static ZS_HD int acc_row(int q, int v) { return 4 * q + v; }
-};
-template <> struct TopicTile<double> {
-  static constexpr int PANEL = 32, LD = PANEL + 17;
-  static ZS_HD int acc_row(int q, int v) { return 4 * v + q; }
-};
-
-ZS_HD int topic_panel_cols(int elem_bytes) { return elem_bytes == 4 ? TopicTile<float>::PANEL : (elem_bytes == 8 ? TopicTile<double>::PANEL : 0); }
-ZS_HD int64_t topic_k16(int64_t K) { return (K + 15) / 16 * 16; }          // rows of the staged panel, row stride of E
+ZS_HD int64_t topic_k16(int64_t K) { return blocks16(K) * 16; }          // rows of the staged panel, row stride of E
 ZS_HD int topic_steps(int64_t K) { return (int)((K + 3) / 4); }
-ZS_HD int64_t topic_panels(int elem_bytes, int64_t V) {
-  const int p = topic_panel_cols(elem_bytes);
-  return (p == 0 || V < 1) ? 0 : (V + p - 1) / p;
-}
 ZS_HD int64_t topic_doc_splits(int elem_bytes, int64_t R, int64_t V) {
-  const int64_t panels = topic_panels(elem_bytes, V);
+  const int64_t panels = zs::panels(elem_bytes, V);
   if (panels == 0 || R < 1) return 0;
   const int64_t blocks = (R + ZS_TOPIC_ROWS_PER_BLOCK - 1) / ZS_TOPIC_ROWS_PER_BLOCK;
   const int64_t s = (ZS_TOPIC_GRID_TARGET + blocks - 1) / blocks;
