@@ -19,6 +19,7 @@ explicit inverse costs a second conditioning factor: with M_L = |L^-1| |L| the c
   gX      |g| e_S + u |g S|;     gmean  sum_k |g| e_S + (2 K + 3) u sum_k |g S|      (a k-sum: at most K terms and K shares)
   gU      sum_k |g| (e_B |A|^T + |B| e_A^T) + (p + 2 K + 8) u (sum_k |g| |B| |A|^T + diag(p sum_k |g| / U_ii));  gV alike with n, C^T A
   M1 bwd  gmean (2 K + 3) u sum_k |gZ|;  gU (2 p + 2 K + 8) u (sum_k |gZ| |V| |E|^T + diag);  gV (2 n + 2 K + 8) u (sum_k |gZ|^T |U| |E| + diag)"""
+import functools
 import math
 
 import numpy as np
@@ -171,6 +172,7 @@ def assert_close(name, got, want, tol):
     print("%s: worst error / tolerance = %.3f" % (name, ratio))
     assert bool(torch.isfinite(got).all()), "%s: non-finite values" % name
     assert bool((err <= tol).all()), "%s: %d elements out of tolerance, worst error / tolerance %.3f" % (name, int((err > tol).sum()), ratio)
+    return ratio
 
 
 def same(a, b, what):
@@ -179,10 +181,21 @@ def same(a, b, what):
         assert same_bits(x, y), what
 
 
-@pytest.mark.parametrize("n,p,R,K,dtypes", CASES)
-def test_forward_and_backward_against_float64(lib, main_lib, n, p, R, K, dtypes):
+GOT = ("z", "lp1", "gm1", "gu1", "gv1", "lp2", "gx", "gm2", "gu2", "gv2", "lpz")
+
+
+@functools.lru_cache(maxsize=2)
+def case_truth(n, p, R, K):
+    """the inputs of a shape and their truth, computed once and left unchanged"""
     d = case_inputs(n, p, R, K)
-    t = truth(d)
+    return d, truth(d)
+
+
+def check_case(lib, main_lib, n, p, R, K, dtypes):
+    """M1, M2 and both backwards in both layouts, twice, against the truth.  Returns ({dtype: {name of GOT: result of the aligned
+    layout, on the CPU}}, {name: worst error / tolerance})."""
+    d, t = case_truth(n, p, R, K)
+    outs, worst = {}, {}
     count, seed, call = K * R * n * p, 11 + n, 3 + p
     rs = torch.tensor((77, 1 << 33), dtype=I64, device=DEV) if (n + p) % 2 else None          # the launch's stream by value, or by rng_state
     noise = torch.empty(count, dtype=F32, device=DEV)
@@ -206,18 +219,25 @@ def test_forward_and_backward_against_float64(lib, main_lib, n, p, R, K, dtypes)
             res.append([a.cpu() for a in one[1:] + two[1:] + at_z[1:2]])
         for a, b in zip(*res):
             assert same_bits(a, b), "the aligned and the shifted layout differ"
-        got = dict(zip(("z", "lp1", "gm1", "gu1", "gv1", "lp2", "gx", "gm2", "gu2", "gv2", "lpz"), res[0]))
+        got = dict(zip(GOT, res[0]))
         tol = bounds(dtype, d, t, K)
         tag = " [n=%d p=%d R=%d K=%d %s]" % (n, p, R, K, sfx(dtype))
         for k in ("gu1", "gu2", "gv1", "gv2"):
             dim = n if k[1] == "u" else p
             assert bool((torch.triu(got[k].view(R, dim, dim), 1) == 0).all()), "%s: the upper triangle is not exactly zero" % k
         for k in ("z", "lp1", "gm1", "gu1", "gv1", "lp2", "gx", "gm2", "gu2", "gv2"):
-            assert_close(k + tag, got[k], t[k], tol[k])
+            worst[k + sfx(dtype)] = assert_close(k + tag, got[k], t[k], tol[k])
         # M2 at M1's own z against M1's lp: within the sum of the two bounds
         zd = got["z"].to(F64).view(K, R, n, p)
         tz = truth(d, zd)
         assert_close("lp(z)" + tag, got["lpz"], got["lp1"].to(F64).view(K, R), tol["lp1"] + bounds(dtype, d, tz, K, zd)["lp2"])
+        outs[dtype] = got
+    return outs, worst
+
+
+@pytest.mark.parametrize("n,p,R,K,dtypes", CASES)
+def test_forward_and_backward_against_float64(lib, main_lib, n, p, R, K, dtypes):
+    check_case(lib, main_lib, n, p, R, K, dtypes)
     print("worst error / tolerance so far: %s" % ", ".join("%s %.3f" % kv for kv in sorted(WORST.items())))
 
 

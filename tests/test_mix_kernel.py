@@ -29,6 +29,7 @@ responsibilities exp(s - lp):
   dlogstd  w [ e_GY2 + 2 |nu| e_GY + nu^2 e_n ] + e_n + u (E_w + 8) [ w (sum|G y^2| + 2 |nu| sum|G y| + nu^2 sum|G|) + sum|G| ]
   dlogits  e_n + u (R + 24 + C + 2 (max|logits| + |lsm|)) (sum|G| + pi_c sum|g|) + tiny (sum|g| + 2)
 each times RATIO, the gradients plus 2 tiny."""
+import functools
 import math
 
 import numpy as np
@@ -132,18 +133,27 @@ def assert_close(name, got, want, tol):
     print("%s: worst error / tolerance = %.3f" % (name, ratio))
     assert bool(torch.isfinite(got).all()), "%s: non-finite values" % name
     assert bool((err <= tol).all()), "%s: %d elements out of tolerance, worst error / tolerance %.3f" % (name, int((err > tol).sum()), ratio)
+    return ratio
 
 
-@pytest.mark.parametrize("D,C,R", CASES)
-def test_forward_and_backward_against_float64(lib, D, C, R):
+@functools.lru_cache(maxsize=2)
+def case_truth(D, C, R):
+    """the inputs of a shape and their truth, computed once and left unchanged"""
     ins = case_inputs(D, C, R)
-    t = truth(*ins)
+    return ins, truth(*ins)
+
+
+def check_case(lib, D, C, R, shares=None):
+    """Both element types, both layouts, twice, against the truth; `shares` = None takes the library's own zs_mix_row_shares.
+    Returns ({dtype: [lp, dx, dlogits, dmean, dlogstd] of the aligned layout, on the CPU}, {name: worst error / tolerance})."""
+    ins, t = case_truth(D, C, R)
+    outs, worst = {}, {}
     for dtype in (F32, F64):
         res = []
         for shift in (0, 1):
             ar = Arena(shift)
             ops = [ar.put(a, dtype) for a in ins]
-            first, again = run(lib, dtype, ar, ops, R, C, D), run(lib, dtype, ar, ops, R, C, D)
+            first, again = run(lib, dtype, ar, ops, R, C, D, shares), run(lib, dtype, ar, ops, R, C, D, shares)
             ar.check_guards()
             assert first[0] == [0] * 4 and again[0] == [0] * 4
             for a, b in zip(first[1], again[1]):
@@ -153,10 +163,17 @@ def test_forward_and_backward_against_float64(lib, D, C, R):
             assert same_bits(a, b), "the aligned and the shifted layout differ"
         tag, tols = " [D=%d C=%d R=%d %s]" % (D, C, R, sfx(dtype)), bounds(dtype, *ins, t)
         for name, got, tol in zip(NAMES, res[0], tols):
-            assert_close(name + tag, got, t[name], tol)          # (finite too: the lowered component's rows, the far row)
+            worst[name + sfx(dtype)] = assert_close(name + tag, got, t[name], tol)          # (finite too: the lowered component's rows, the far row)
         if C == 1:
             plain = torch.distributions.Normal(ins[1][0], torch.exp(ins[2][0])).log_prob(ins[3]).sum(-1)
             assert_close("lp against the diagonal normal" + tag, res[0][0], plain, tols[0])
+        outs[dtype] = res[0]
+    return outs, worst
+
+
+@pytest.mark.parametrize("D,C,R", CASES)
+def test_forward_and_backward_against_float64(lib, D, C, R):
+    check_case(lib, D, C, R)
     print("worst error / tolerance so far: %s" % ", ".join("%s %.3f" % kv for kv in sorted(WORST.items())))
 
 

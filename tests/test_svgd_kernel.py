@@ -97,10 +97,13 @@ def close(name, got, want, tol):
     err = float(((got - want).abs() / torch.as_tensor(tol, dtype=F64)).max())
     print("%s: worst error / tolerance = %.3f" % (name, err))
     assert bool(torch.isfinite(got).all()) and err <= 1.0, "%s: worst error / tolerance %.3f" % (name, err)
+    return err
 
 
-def check_step(lib, dtype, K, thetas, grads, bandwidth, tag):
-    """one step on both alignments, twice, and aliased; against the truth"""
+def check_step(lib, dtype, K, thetas, grads, bandwidth, tag, worst=None):
+    """one step on both alignments, twice, and aliased; against the truth.  `worst`, a dict, receives the worst error / tolerance
+    of the kernel matrix, of h and of the moved particles."""
+    worst = {} if worst is None else worst
     t = truth(thetas, grads, bandwidth)
     bphi, bk, bh = bounds(dtype, thetas, grads, t, bandwidth)
     res = []
@@ -121,11 +124,11 @@ def check_step(lib, dtype, K, thetas, grads, bandwidth, tag):
     n = len(thetas)
     k = res[0][n]
     assert bool((torch.diagonal(k) == 1).all()) and bool((k == k.t()).all()), "the kernel matrix: unit diagonal, symmetric"
-    close("kernel" + tag, k, t[1], bk)
-    close("h" + tag, res[0][n + 1], torch.tensor(t[2], dtype=F64), bh)
+    worst["kernel"] = close("kernel" + tag, k, t[1], bk)
+    worst["h"] = close("h" + tag, res[0][n + 1], torch.tensor(t[2], dtype=F64), bh)
     for i in range(n):
         want = thetas[i] + STEP * t[0][i]
-        close("q_out[%d]" % i + tag, res[0][i], want, STEP * bphi + 2 * unit(dtype) * want.abs())
+        worst["q_out"] = max(worst.get("q_out", 0.0), close("q_out[%d]" % i + tag, res[0][i], want, STEP * bphi + 2 * unit(dtype) * want.abs()))
     return t
 
 
