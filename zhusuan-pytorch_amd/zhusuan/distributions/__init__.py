@@ -12,7 +12,8 @@ dropped them) run on the categorical kernels of include/zs_cat.h, a library of i
 MultivariateNormalCholesky (the same history) runs on the triangular kernels of include/zs_mvn.h, likewise.  AdmixtureMultinomial
 (the likelihood of the reference's unfinished logistic-normal topic model) runs on the matrix-core kernels of include/zs_topic.h,
 MatrixVariateNormalCholesky (upstream has it, the reference dropped it) on those of include/zs_matvar.h, NormalMixture (a
-mixture-of-Gaussians / VampPrior density) on those of include/zs_mix.h."""
+mixture-of-Gaussians / VampPrior density) on those of include/zs_mix.h, MultivariateNormalLowRank (covariance diag + W W^T, for
+wide flat latents) on those of include/zs_lowrank.h."""
 from .base import Distribution
 from .normal import Normal
 from .bernoulli import Bernoulli
@@ -25,6 +26,7 @@ from .multivariate import MultivariateNormalCholesky
 from .admixture import AdmixtureMultinomial
 from .matrix_variate import MatrixVariateNormalCholesky
 from .mixture import NormalMixture
+from .lowrank import MultivariateNormalLowRank
 
 __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # torch.distributions pass-throughs (no kernels) and the flow-defined distribution:
@@ -39,4 +41,6 @@ __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # the matrix-variate normal (include/zs_matvar.h):
            'MatrixVariateNormalCholesky',
            # the mixture of Gaussians (include/zs_mix.h):
-           'NormalMixture']
+           'NormalMixture',
+           # the low-rank multivariate normal (include/zs_lowrank.h):
+           'MultivariateNormalLowRank']

@@ -6,7 +6,7 @@ import torch.nn as nn
 from .stochastic_tensor import StochasticTensor, node_value
 from ..distributions import (Distribution, Normal, Bernoulli, Logistic, Uniform, Beta, Exponential, Gamma, Laplace, Poisson,
                              StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete, MultivariateNormalCholesky,
-                             AdmixtureMultinomial, MatrixVariateNormalCholesky, NormalMixture)
+                             AdmixtureMultinomial, MatrixVariateNormalCholesky, NormalMixture, MultivariateNormalLowRank)
 
 __all__ = ['BayesianNet']
 
@@ -249,3 +249,10 @@ class BayesianNet(nn.Module):
         return self._family_node(NormalMixture, name, n_samples,
                                  dict(logits=logits, mean=mean, std=std, logstd=logstd, batch_shape=batch_shape, dtype=dtype,
                                       group_ndims=group_ndims), kwargs)
+
+    # include/zs_lowrank.h: a normal over D-vectors with covariance diag(cov_diag) + cov_factor cov_factor^T (wide flat latents)
+    def multivariate_normal_low_rank(self, name, mean, cov_factor, cov_diag, dtype=None, is_reparameterized=True, group_ndims=0,
+                                     n_samples=None, **kwargs):
+        return self._family_node(MultivariateNormalLowRank, name, n_samples,
+                                 dict(mean=mean, cov_factor=cov_factor, cov_diag=cov_diag, dtype=dtype,
+                                      is_reparameterized=is_reparameterized, group_ndims=group_ndims), kwargs)
