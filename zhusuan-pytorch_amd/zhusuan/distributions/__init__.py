@@ -13,7 +13,8 @@ MultivariateNormalCholesky (the same history) runs on the triangular kernels of 
 (the likelihood of the reference's unfinished logistic-normal topic model) runs on the matrix-core kernels of include/zs_topic.h,
 MatrixVariateNormalCholesky (upstream has it, the reference dropped it) on those of include/zs_matvar.h, NormalMixture (a
 mixture-of-Gaussians / VampPrior density) on those of include/zs_mix.h, MultivariateNormalLowRank (covariance diag + W W^T, for
-wide flat latents) on those of include/zs_lowrank.h."""
+wide flat latents) on those of include/zs_lowrank.h, GPConditional (the predictive moments of a sparse Gaussian process) on those of
+include/zs_gp.h."""
 from .base import Distribution
 from .normal import Normal
 from .bernoulli import Bernoulli
@@ -27,6 +28,7 @@ from .admixture import AdmixtureMultinomial
 from .matrix_variate import MatrixVariateNormalCholesky
 from .mixture import NormalMixture
 from .lowrank import MultivariateNormalLowRank
+from .gp import GPConditional
 
 __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # torch.distributions pass-throughs (no kernels) and the flow-defined distribution:
@@ -43,4 +45,6 @@ __all__ = ['Distribution', 'Normal', 'Bernoulli', 'Logistic', 'Uniform',
            # the mixture of Gaussians (include/zs_mix.h):
            'NormalMixture',
            # the low-rank multivariate normal (include/zs_lowrank.h):
-           'MultivariateNormalLowRank']
+           'MultivariateNormalLowRank',
+           # the sparse-GP conditional (include/zs_gp.h):
+           'GPConditional']

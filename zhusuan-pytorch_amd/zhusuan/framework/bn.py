@@ -6,7 +6,7 @@ import torch.nn as nn
 from .stochastic_tensor import StochasticTensor, node_value
 from ..distributions import (Distribution, Normal, Bernoulli, Logistic, Uniform, Beta, Exponential, Gamma, Laplace, Poisson,
                              StudentT, Categorical, OnehotCategorical, ExpConcrete, Concrete, MultivariateNormalCholesky,
-                             AdmixtureMultinomial, MatrixVariateNormalCholesky, NormalMixture, MultivariateNormalLowRank)
+                             AdmixtureMultinomial, MatrixVariateNormalCholesky, NormalMixture, MultivariateNormalLowRank, GPConditional)
 
 __all__ = ['BayesianNet']
 
@@ -256,3 +256,11 @@ class BayesianNet(nn.Module):
         return self._family_node(MultivariateNormalLowRank, name, n_samples,
                                  dict(mean=mean, cov_factor=cov_factor, cov_diag=cov_diag, dtype=dtype,
                                       is_reparameterized=is_reparameterized, group_ndims=group_ndims), kwargs)
+
+    # include/zs_gp.h: the predictive normal of a sparse Gaussian process at x given f_inducing (upstream's gp_conditional)
+    def gp_conditional(self, name, x, inducing, f_inducing, kzz_tril, lengthscale, amplitude, dtype=None, is_reparameterized=True,
+                       group_ndims=0, n_samples=None, **kwargs):
+        return self._family_node(GPConditional, name, n_samples,
+                                 dict(x=x, inducing=inducing, f_inducing=f_inducing, kzz_tril=kzz_tril, lengthscale=lengthscale,
+                                      amplitude=amplitude, dtype=dtype, is_reparameterized=is_reparameterized,
+                                      group_ndims=group_ndims), kwargs)
